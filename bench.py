@@ -8,7 +8,14 @@ Metric (BASELINE.json): "MPI_Allreduce busbw GB/s (1 GiB fp32, np=8) + op/hip re
   N > 1  (configs[2] at 1 GiB): MPI_Allreduce MPI_SUM fp32 1 GiB per rank through coll/mi355x's
          engine over IPC-mapped peers; value = busbw = (S/t) x 2(n-1)/n, max time over ranks.
 
-Launch: `python bench.py --gpus N --steps K --warmup W`.  N > 1 runs one rank per GPU: under
+Launch: `python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]`.  A plain run
+sets up, warms up, times the K steps, writes its outputs if asked to and prints the result line.
+--full adds everything else the benchmark measures or checks (N = 1: the parity check of the measured
+kernel, the configs[1] slot sweep and the CPU baseline; N > 1: the per-kernel roofline figures, the
+link measurement, the other configs' legs and the CPU baseline).  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy (float32; a fixed, seeded sample of the 1 GiB result);
+the inputs are seeded, so two builds can be compared output for output.
+N > 1 runs one rank per GPU: under
 torch.distributed.run as the driver launches it, or -- with no launcher environment -- bench.py starts
 torch.distributed.run itself as a child process and forwards rank 0's line (spawn_ranks).
 Rank 0 prints ONE JSON line.  Timed region = exactly K steps between barrier+synchronize pairs.
@@ -106,12 +113,38 @@ def cpu_baseline_op(target_s: float = 10.0):
     return out
 
 
+DUMP_SEED = 20240
+DUMP_EDGE = 4096
+
+
+def sample_index(n: int, k: int):
+    """The fixed sample --dump-outputs takes of an n-element result: the first and last DUMP_EDGE
+    elements and k seeded draws between them, ascending (int64 numpy array)."""
+    import numpy as np
+    if n <= k + 2 * DUMP_EDGE:
+        return np.arange(n, dtype=np.int64)
+    mid = np.random.default_rng(DUMP_SEED).integers(DUMP_EDGE, n - DUMP_EDGE, size=k, dtype=np.int64)
+    return np.concatenate([np.arange(DUMP_EDGE, dtype=np.int64), np.sort(mid),
+                           np.arange(n - DUMP_EDGE, n, dtype=np.int64)])
+
+
+def dump_output(torch, dirname: str, name: str, t, k: int) -> None:
+    """DIR/<name>.npy: the sample_index elements of device tensor t, float32"""
+    import numpy as np
+    d = pathlib.Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    idx = torch.from_numpy(sample_index(t.numel(), k)).to(t.device)
+    np.save(d / f"{name}.npy", t.index_select(0, idx).to(torch.float32).cpu().numpy())
+
+
 def bench_op(args, pkg, torch):
     """N = 1: op/hip 3-buff SUM fp32, 1 GiB per operand."""
     n = GIB // 4
     dev = torch.device("cuda", 0)
-    a = torch.randn(n, device=dev, dtype=torch.float32)
-    b = torch.randn(n, device=dev, dtype=torch.float32)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)  # the same operands every run
+    a = torch.randn(n, device=dev, dtype=torch.float32, generator=gen)
+    b = torch.randn(n, device=dev, dtype=torch.float32, generator=gen)
     o = torch.empty_like(a)
     s = torch.cuda.current_stream()
     sh = s.cuda_stream
@@ -120,8 +153,9 @@ def bench_op(args, pkg, torch):
     for _ in range(args.warmup):
         pkg.op_reduce_3buff(op, ty, pa, pb, po, n, sh)
     torch.cuda.synchronize()
-    # parity spot-check of the measured kernel on the real size (size-independent property)
-    assert torch.equal(o, a + b), "op/hip SUM result differs from a + b"
+    if args.full and args.warmup > 0:
+        # parity spot-check of the measured kernel on the real size (size-independent property)
+        assert torch.equal(o, a + b), "op/hip SUM result differs from a + b"
     # One HIP event pair on the launch stream brackets the K launches of the timed region; the
     # kernel's average = their span / K (it includes the ~1.5 us launch boundaries, so it bounds
     # the kernel's own time from above; rocprofv3's per-launch average agrees within 1 %).  An
@@ -149,6 +183,9 @@ def bench_op(args, pkg, torch):
     e1.record(s)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    if args.dump_outputs:
+        # the last timed step's result, before the sweep reuses the buffers
+        dump_output(torch, args.dump_outputs, "op_3buff_sum_float_out", o, 1 << 22)
     avg_ms = e0.elapsed_time(e1) / args.steps
     alg_bytes = 3 * n * 4
     value = alg_bytes * args.steps / wall / 1e9
@@ -158,7 +195,7 @@ def bench_op(args, pkg, torch):
     config = {"workload": "op/hip 3-buff MPI_SUM MPI_FLOAT, 1 GiB per operand (BASELINE configs[1])",
               "count": n, "bytes_per_operand": n * 4, "launch": {"unroll": u, "blocks_per_cu": bpc,
                                                                   "nontemporal": nt}}
-    if not args.no_sweep:
+    if args.full and not args.no_sweep:
         # the rest of configs[1] (every slot, both forms), timed after the headline's region
         config["sweep"] = sweep_op(pkg, torch, a, b, o)
     return {
@@ -297,6 +334,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: parity check, sweep / legs, roofline "
+                         "runs, CPU baseline (the --no-* options below take parts of it out again)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", action="store_true", help="N = 1: replay the K timed launches as one HIP graph")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -307,6 +349,8 @@ def main():
     ap.add_argument("--legs-timeout", type=float, default=300.0,
                     help="N > 1: seconds after which the legs are abandoned and the headline printed")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: start the ranks ourselves (child process, nothing GPU-side touched yet)
@@ -323,7 +367,7 @@ def main():
             return
     else:
         res = bench_op(args, pkg, torch)
-        res["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline_op(args.cpu_seconds)
+        res["cpu_baseline"] = cpu_baseline_op(args.cpu_seconds) if args.full and not args.no_cpu_baseline else None
     print(json.dumps(res), flush=True)
     if res.get("value") is None:  # a failed exactness check or a hung leg: not a valid measurement
         sys.exit(2)

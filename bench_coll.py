@@ -5,6 +5,9 @@ Launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --g
 torch.distributed (gloo, CPU) is used only for the launcher's rendezvous, the timing barrier and
 the max-over-ranks reduction; every byte of the collective moves through the HIP engine.
 value = busbw = (S / t) * 2 (n - 1) / n with S = 1 GiB and t = max over ranks per step.
+A plain run autotunes the data flow (the headline is the best candidate's), times the steps and
+prints the line; the roofline entry (runs of the dominant kernel, the link measurement), the other
+configs' legs and the CPU baseline are measured under --full only.
 """
 from __future__ import annotations
 
@@ -313,7 +316,9 @@ def run(args, pkg, torch):
                                           sync=torch.cuda.synchronize, ok=ok)
     # timed data: N(0,1), order-dependent (the engine replicates the segmented-ring order)
     _log(rank, f"timed: {args.steps} steps, best {best}")
-    x.normal_()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(100 + rank)  # the same operands every run
+    x.normal_(generator=gen)
     torch.cuda.synchronize()
     for _ in range(args.warmup):
         comm.allreduce(x.data_ptr(), y.data_ptr(), n, ty, op)
@@ -331,6 +336,71 @@ def run(args, pkg, torch):
     dt, bad = float(t[0]), float(t[1])
     per = dt / args.steps
     busbw = (n * 4 / per) * 2 * (world - 1) / world / 1e9
+    if getattr(args, "dump_outputs", None):
+        # every rank's result of the last timed step (a fixed, seeded sample of it)
+        import bench
+        bench.dump_output(torch, args.dump_outputs, f"allreduce_out_rank{rank}", y, 1 << 20)
+    full = bool(getattr(args, "full", False))
+    res = {
+        "metric": "MPI_Allreduce busbw GB/s (1 GiB fp32, np=8) + op/hip reduce HBM GB/s",
+        "value": round(busbw, 2),
+        "unit": "GB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(per * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (torch normal_ on device)",
+        "config": {"workload": f"MPI_Allreduce MPI_SUM MPI_FLOAT 1 GiB per rank, np={world} (BASELINE configs[2])",
+                   "count": n, "algorithm": {3: "recursive_doubling", 4: "ring", 5: "segmented_ring"}.get(alg, alg),
+                   "exact_check": "ok" if bad == 0 else "FAILED",
+                   "data_flow": "pipelined (fold + pulls, device flags)" if best["pipe"] else "two-phase pull",
+                   "best": best, "autotune_ms_per_call": tried},
+        # the dominant kernel's own runs and the link measurement: --full
+        "roofline": roofline(args, pkg, torch, dist, comm, x, y, n, ty, op, world, rank, dev, key, best, busbw)
+                    if full else None,
+        "cpu_baseline": None,
+        "legs": None,
+    }
+    if full and not args.no_legs:
+        del x, y
+        torch.cuda.empty_cache()
+        legs = {}
+        # watchdog: a leg that never returns must not take the headline line with it
+        done = threading.Event()
+
+        def watchdog():
+            if not done.wait(args.legs_timeout):
+                if rank == 0:
+                    legs["error"] = f"legs exceeded {args.legs_timeout:.0f} s; partial results above"
+                    res["legs"] = legs
+                    print(json.dumps(res), flush=True)
+                os._exit(3)  # a hung leg is a failed run, whatever the headline said
+        threading.Thread(target=watchdog, daemon=True).start()
+        try:
+            extra_legs(args, pkg, torch, comm, world, rank, dev, legs, key)
+        except Exception as e:  # a failing extra leg must not hide the headline line
+            legs["error"] = repr(e)[:300]
+        done.set()
+        res["legs"] = legs
+    comm.destroy()
+    if rank != 0:
+        dist.destroy_process_group()
+        return None
+    dist.destroy_process_group()
+    if full and not args.no_cpu_baseline:
+        res["cpu_baseline"] = cpu_baseline_ring(world, args.cpu_seconds)
+    if bad != 0:  # a wrong result is not a measurement
+        res["error"] = "allreduce result differs from the exact sum"
+        res["value"] = None
+    return res
+
+
+def roofline(args, pkg, torch, dist, comm, x, y, n, ty, op, world, rank, dev, key, best, busbw):
+    """the roofline entry of the N > 1 line (--full): runs of its own after the timed region"""
     # dominant kernel (phase 1, k_fold: the owner folds its block from all n ranks), timed with
     # HIP events on the call's stream over 5 untimed-region calls; max over ranks
     comm.set("TIME_PHASES", 1)
@@ -363,82 +433,30 @@ def run(args, pkg, torch):
     link_gbs = link.get("GBs_per_direction") if link and link.get("exact") else None
     peak_spec = (world - 1) * XGMI_LINK_DIR_GBS
     peak_all = (world - 1) * link_gbs if link_gbs else peak_spec
-    res = {
-        "metric": "MPI_Allreduce busbw GB/s (1 GiB fp32, np=8) + op/hip reduce HBM GB/s",
-        "value": round(busbw, 2),
-        "unit": "GB/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(per * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (torch normal_ on device)",
-        "config": {"workload": f"MPI_Allreduce MPI_SUM MPI_FLOAT 1 GiB per rank, np={world} (BASELINE configs[2])",
-                   "count": n, "algorithm": {3: "recursive_doubling", 4: "ring", 5: "segmented_ring"}.get(alg, alg),
-                   "exact_check": "ok" if bad == 0 else "FAILED",
-                   "data_flow": "pipelined (fold + pulls, device flags)" if pipe else "two-phase pull",
-                   "best": best, "autotune_ms_per_call": tried},
-        "roofline": ({"bound": "xgmi", "achieved": round(fold_xgmi, 2), "peak": round(peak_all, 1), "unit": "GB/s",
-                      "frac": round(fold_xgmi / peak_all, 4), "traffic": pmc_traffic(pipe, shared=False, world=world),
-                      "traffic_note": "HBM bytes per launch from a committed rocprofv3 PMC summary of this "
-                                      "kernel on separate GPUs, or null: only the one-GPU rehearsal's "
-                                      "(profiles/r02_pmc_rehearsal_n*.json) exists so far",
-                      "kernel": kname, "kernel_avg_ms": round(p1, 4),
-                      "alg_bytes_per_launch": int(xgmi_bytes), "phase2_ms": round(p2, 4),
-                      "busbw_frac": round(busbw / peak_all, 4),
-                      # against one ring (one link per direction) as well as all n-1
-                      "busbw_frac_ring1": round(busbw / (link_gbs or XGMI_LINK_DIR_GBS), 4),
-                      "peak_spec": round(peak_spec, 1), "frac_spec": round(fold_xgmi / peak_spec, 4),
-                      "link": link,
-                      "peak_note": (f"(n-1) links x {link_gbs} GB/s per direction, measured (link.GBs_per_direction)"
-                                    if link_gbs else f"(n-1) links x {XGMI_LINK_DIR_GBS} GB/s per direction (spec; "
-                                    "the link measurement failed)") + "; achieved = the remote bytes one launch "
-                                   "reads over xGMI / its event time"} if not shared else
-                     {"bound": "hbm", "achieved": round(fold_hbm, 2), "peak": 8000.0, "unit": "GB/s",
-                      "frac": round(fold_hbm / 8000.0, 4), "traffic": pmc_traffic(pipe, shared=True, world=world),
-                      "kernel": kname, "kernel_avg_ms": round(p1, 4),
-                      "alg_bytes_per_launch": int(hbm_bytes / world), "phase2_ms": round(p2, 4),
-                      "peak_note": "REHEARSAL: all ranks share one GPU, no xGMI traffic: the n concurrent "
-                                   "launches' HBM reads + writes (n x alg_bytes_per_launch) against the "
-                                   "chip's HBM; busbw not valid"}),
-        "cpu_baseline": None,
-        "legs": None,
-    }
-    if not args.no_legs:
-        del x, y
-        torch.cuda.empty_cache()
-        legs = {}
-        # watchdog: a leg that never returns must not take the headline line with it
-        done = threading.Event()
-
-        def watchdog():
-            if not done.wait(args.legs_timeout):
-                if rank == 0:
-                    legs["error"] = f"legs exceeded {args.legs_timeout:.0f} s; partial results above"
-                    res["legs"] = legs
-                    print(json.dumps(res), flush=True)
-                os._exit(3)  # a hung leg is a failed run, whatever the headline said
-        threading.Thread(target=watchdog, daemon=True).start()
-        try:
-            extra_legs(args, pkg, torch, comm, world, rank, dev, legs, key)
-        except Exception as e:  # a failing extra leg must not hide the headline line
-            legs["error"] = repr(e)[:300]
-        done.set()
-        res["legs"] = legs
-    comm.destroy()
-    if rank != 0:
-        dist.destroy_process_group()
-        return None
-    dist.destroy_process_group()
-    if not args.no_cpu_baseline:
-        res["cpu_baseline"] = cpu_baseline_ring(world, args.cpu_seconds)
-    if bad != 0:  # a wrong result is not a measurement
-        res["error"] = "allreduce result differs from the exact sum"
-        res["value"] = None
-    return res
+    if shared:  # REHEARSAL: the chip's HBM is the bound
+        return {"bound": "hbm", "achieved": round(fold_hbm, 2), "peak": 8000.0, "unit": "GB/s",
+                "frac": round(fold_hbm / 8000.0, 4), "traffic": pmc_traffic(pipe, shared=True, world=world),
+                "kernel": kname, "kernel_avg_ms": round(p1, 4),
+                "alg_bytes_per_launch": int(hbm_bytes / world), "phase2_ms": round(p2, 4),
+                "peak_note": "REHEARSAL: all ranks share one GPU, no xGMI traffic: the n concurrent "
+                             "launches' HBM reads + writes (n x alg_bytes_per_launch) against the "
+                             "chip's HBM; busbw not valid"}
+    return {"bound": "xgmi", "achieved": round(fold_xgmi, 2), "peak": round(peak_all, 1), "unit": "GB/s",
+            "frac": round(fold_xgmi / peak_all, 4), "traffic": pmc_traffic(pipe, shared=False, world=world),
+            "traffic_note": "HBM bytes per launch from a committed rocprofv3 PMC summary of this "
+                            "kernel on separate GPUs, or null: only the one-GPU rehearsal's "
+                            "(profiles/r02_pmc_rehearsal_n*.json) exists so far",
+            "kernel": kname, "kernel_avg_ms": round(p1, 4),
+            "alg_bytes_per_launch": int(xgmi_bytes), "phase2_ms": round(p2, 4),
+            "busbw_frac": round(busbw / peak_all, 4),
+            # against one ring (one link per direction) as well as all n-1
+            "busbw_frac_ring1": round(busbw / (link_gbs or XGMI_LINK_DIR_GBS), 4),
+            "peak_spec": round(peak_spec, 1), "frac_spec": round(fold_xgmi / peak_spec, 4),
+            "link": link,
+            "peak_note": (f"(n-1) links x {link_gbs} GB/s per direction, measured (link.GBs_per_direction)"
+                          if link_gbs else f"(n-1) links x {XGMI_LINK_DIR_GBS} GB/s per direction (spec; "
+                          "the link measurement failed)") + "; achieved = the remote bytes one launch "
+                         "reads over xGMI / its event time"}
 
 
 def apply_cand(comm, cand):

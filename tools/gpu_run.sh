@@ -7,12 +7,12 @@
 #   suite          pytest -m gpu (whole suite) + smoke()               -> pytest_gpu.log, smoke.log
 #   tests          pytest -m gpu on $TESTS (node ids / files), -k "$K" -> pytest_sel.log
 #   smoke          __graft_entry__.smoke()
-#   bench          python bench.py (N = 1 headline line)               -> bench_n1.json
+#   bench          python bench.py --full (N = 1 line with sweep and CPU baseline) -> bench_n1.json
 #   prof_bench     rocprofv3 --kernel-trace --stats of the N = 1 bench -> prof_bench/
 #   pmc            FETCH_SIZE / WRITE_SIZE passes (separate runs) of the N = 1 bench -> pmc_op.json
 #   legs           tools/bench_legs.py --legs $LEGS (default op,ddt)   -> legs.jsonl
 #   prof_ddt       rocprofv3 kernel trace of the convertor legs         -> prof_ddt/
-#   rehearse       bench.py --gpus N self-launch for N in $NS (default "2 8"; ranks share the GPU)
+#   rehearse       bench.py --gpus N --full self-launch for N in $NS (default "2 8"; ranks share the GPU)
 #   small          small collectives from C (tools/build/small_ar_c), np in $NS (default "2 4"),
 #                  $SMALL_COLL (allreduce), $SMALL_SIZES, $PATHS (host,ll,svc), $REPS -> small.jsonl
 #   svc_trace      the service's per-stage times at 8 B and 64 KiB (MI355X_SVC_TRACE=1)
@@ -56,7 +56,7 @@ run() {  # run NAME LIMIT CMD...: output to $O/NAME.log, tail on failure, exit o
 ranks_bench() {  # ranks_bench NAME PROFILER_ARGS... -- rank 0 of an N-rank bench.py run under rocprofv3
     local name=$1
     shift
-    local args="--gpus $N --steps ${STEPS:-10} --warmup 3 --no-legs --no-cpu-baseline ${EXTRA:-}"
+    local args="--gpus $N --steps ${STEPS:-10} --warmup 3 --full --no-legs --no-cpu-baseline ${EXTRA:-}"
     local pids=() rcs=0 r
     port=$((port + 1))
     for r in $(seq 1 $((N - 1))); do
@@ -100,7 +100,7 @@ for step in "$@"; do
         run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
         tail -2 $O/smoke.log ;;
     bench)
-        run bench_n1 300 python bench.py --steps ${STEPS:-20} --warmup ${WARM:-5}
+        run bench_n1 300 python bench.py --full --steps ${STEPS:-20} --warmup ${WARM:-5}
         grep '^{' $O/bench_n1.log | tail -1 > $O/bench_n1.json
         cut -c1-600 $O/bench_n1.json ;;
     bench_ab)  # N = 1: the K timed launches issued one by one vs replayed as one HIP graph, alternated
@@ -113,7 +113,7 @@ for step in "$@"; do
         done ;;
     prof_bench)
         run prof_bench 300 rocprofv3 --kernel-trace --stats -d $O/prof_bench -o run --output-format csv -- \
-            python bench.py --steps 20 --warmup 5 --no-cpu-baseline
+            python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
         head -3 $O/prof_bench/run_kernel_stats.csv | cut -c1-200 ;;
     pmc)
         run pmc_f 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_f -o run --output-format csv -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline
@@ -127,7 +127,7 @@ for step in "$@"; do
             python tools/bench_legs.py --legs ddt --no-cpu-baseline --out $O/legs_ddt_prof.jsonl ;;
     rehearse)
         for N in ${NS:-2 8}; do
-            run bench_n$N ${TMO:-420} python bench.py --gpus $N --steps ${STEPS:-10} --warmup 3 ${ARGS:-}
+            run bench_n$N ${TMO:-420} python bench.py --gpus $N --full --steps ${STEPS:-10} --warmup 3 ${ARGS:-}
             grep '^{' $O/bench_n$N.log | tail -1 > $O/bench_n$N.json
             cut -c1-800 $O/bench_n$N.json
         done ;;
