@@ -154,6 +154,7 @@ extern unsigned long long mca_coll_mi355x_svc_copy_max;  /* 1 MiB */
 extern int mca_coll_mi355x_svc_idle_us;                  /* 1000 */
 extern int mca_coll_mi355x_svc_shrink_us;                /* 100 */
 extern int mca_coll_mi355x_selftest;                     /* 1 */
+extern int mca_coll_mi355x_nb_order;                     /* 0: coll/tuned's order for the nonblocking reductions; 1: coll/libnbc's */
 /* the engine of a communicator coll/mi355x serves (NULL otherwise): for tools and tests */
 struct mi355x_comm *mca_coll_mi355x_engine_of(struct ompi_communicator_t *comm);
 

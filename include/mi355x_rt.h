@@ -253,9 +253,15 @@ enum mi355x_knob {
     MI355X_KNOB_EXPORT_MISMATCHES = 42, /* (read-only) new dmabuf exports of the bounded peer-mapping cache that
                                            named another buffer object (checked, that call staged instead;
                                            env MI355X_EXPORT_CHECK=0 turns the check off) */
-    MI355X_KNOB_SELFTEST_REUSED = 43    /* (read-only) flow verdicts this communicator took over from an earlier
+    MI355X_KNOB_SELFTEST_REUSED = 43,   /* (read-only) flow verdicts this communicator took over from an earlier
                                            communicator of the same processes on the same GPUs (a dup / split):
                                            1 the device setup's (LL, pipelined), 2 also the service's */
+    MI355X_KNOB_NB_ORDER = 44           /* (per communicator, same value on every rank; env MI355X_NB_ORDER at
+                                           creation; default 0) operand order of mi355x_iallreduce / _ireduce /
+                                           _ireduce_scatter_block: 0 = coll/tuned's, as the blocking calls; 1 =
+                                           coll/libnbc's, the component that serves them in the reference (its
+                                           own selection, every step the 3-buff rule with the rank's own data
+                                           as in1).  Set only while no nonblocking call is pending. */
 };
 /* cross-device flows (MI355X_KNOB_FLOWS) */
 enum mi355x_flow {
@@ -343,9 +349,15 @@ int mi355x_exscan(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t coun
 /* Nonblocking collectives (MPI_Iallreduce, MPI_Ireduce, MPI_Ireduce_scatter_block, MPI_Iallgather,
  * MPI_Ibcast; the coll framework's nonblocking slots, coll.h:241-356, served in the reference by
  * coll/libnbc: nbc_iallreduce.c etc.).  Each call is queued behind the caller's prior work on
- * `stream` and run, in posting order, by the communicator's progress thread; results are
- * identical to the blocking call's.  A blocking collective on the same communicator first waits
- * for every posted one.  Requests: test (non-blocking; *done = 1 once finished, then returns the
+ * `stream` and run, in posting order, by the communicator's progress thread.  Under
+ * MI355X_KNOB_NB_ORDER = 0 (the default) results are identical to the blocking call's, i.e.
+ * coll/tuned's operand order.  Under NB_ORDER = 1 iallreduce, ireduce and ireduce_scatter_block
+ * give coll/libnbc's results bit for bit instead: binomial or ring (nbc_iallreduce.c:80-85),
+ * binomial or chain (nbc_ireduce.c:74-88), binomial + scatter (coll_libnbc_ireduce_scatter_block.c),
+ * every step ompi_3buff_op_reduce; mi355x_comm_last_algorithm then reports 101 (binomial), 102
+ * (ring) or 103 (chain), and a binomial tree over more than 16 ranks makes the posting call return
+ * MI355X_ERR_UNSUPPORTED.  The other nonblocking calls do not depend on the knob.  A blocking
+ * collective on the same communicator first waits for every posted one.  Requests: test (non-blocking; *done = 1 once finished, then returns the
  * collective's status), wait (blocks; returns the status), free (only once finished). */
 typedef struct mi355x_request mi355x_request_t;
 int mi355x_iallreduce(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t count, int type, int op,
@@ -491,6 +503,11 @@ int mi355x_ddt_raw(const mi355x_ddt_t *d, size_t count, size_t *pos, int64_t *di
 /* Host-only introspection of the schedule compiler: the per-element program the engine runs for
  * a given reference algorithm (layout documented in coll_comm.cpp).  For tests; no GPU needed. */
 int mi355x_sched_program(int kind, int n, int alg, int block, int *out, int cap);
+/* coll/libnbc's selection (101 binomial, 102 ring, 103 chain) for coll 0 = MPI_Iallreduce, 1 =
+ * MPI_Ireduce, 2 = MPI_Ireduce_scatter_block of `bytes` bytes (the whole vector) over n ranks, and
+ * segment e of its ring partition of `count` elements (nbc_iallreduce.c:311-329).  No GPU. */
+int mi355x_nbc_decision(int coll, int n, size_t bytes, int inplace);
+int mi355x_nbc_ring_block(size_t count, int n, int e, size_t *off, size_t *len);
 
 #ifdef __cplusplus
 }

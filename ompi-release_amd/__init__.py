@@ -147,6 +147,8 @@ def _declare(lib: ctypes.CDLL) -> None:
         "mi355x_allgather": (i, [vp, vp, vp, sz, vp]),
         "mi355x_bcast": (i, [vp, vp, sz, i, vp]),
         "mi355x_sched_program": (i, [i, i, i, i, c.POINTER(i), i]),
+        "mi355x_nbc_decision": (i, [i, i, sz, i]),
+        "mi355x_nbc_ring_block": (i, [sz, i, i, c.POINTER(sz), c.POINTER(sz)]),
         "mi355x_rules_load": (i, [c.c_char_p, c.POINTER(vp)]),
         "mi355x_rules_destroy": (i, [vp]),
         "mi355x_rules_decide": (i, [vp, i, i, sz, c.POINTER(i), c.POINTER(i), c.POINTER(i)]),
@@ -265,7 +267,9 @@ KNOB = {"ALLREDUCE_ALG": 1, "REDUCE_ALG": 2, "REDUCE_SCATTER_ALG": 3, "BLOCKS_PE
         "RCACHE_EVICTIONS": 28, "FLOWS": 29, "FLOWS_FAILED": 30, "CREATE_US": 31, "SELFTEST_US": 32,
         "SVC_OWNER": 33, "SVC_CLAIMS": 34, "SVC_IDLE_US": 35,
         "SVC_SHRINK_US": 36, "SVC_REGROWS": 37, "DEV_SETUP": 38, "SETUP_US": 39, "SELFTEST": 40,
-        "PIPE_CALLS": 41, "EXPORT_MISMATCHES": 42, "SELFTEST_REUSED": 43}
+        "PIPE_CALLS": 41, "EXPORT_MISMATCHES": 42, "SELFTEST_REUSED": 43, "NB_ORDER": 44}
+# coll/libnbc's algorithms (mi355x_comm_last_algorithm under NB_ORDER = 1, mi355x_nbc_decision)
+NBC_ALG = {"BINOMIAL": 101, "RING": 102, "CHAIN": 103}
 FLOW = {"SVC_LL": 1, "SVC_PULL": 2, "SVC_COPY": 4, "SVC_RS": 8, "PIPE": 16}
 # coll/tuned COLLTYPE ids (coll_tuned.h:41-58)
 COLL = {"ALLGATHER": 0, "ALLREDUCE": 2, "BCAST": 7, "REDUCE": 11, "REDUCESCATTER": 12}
@@ -652,6 +656,20 @@ def sched_program(kind: int, n: int, alg: int, block: int) -> list[int]:
     k = rt().mi355x_sched_program(kind, n, alg, block, buf, 4096)
     check(0 if k >= 0 else k, "mi355x_sched_program")
     return list(buf[:k])
+
+
+def nbc_decision(coll: int, n: int, nbytes: int, inplace: bool = False) -> int:
+    """coll/libnbc's algorithm (NBC_ALG) for coll 0 iallreduce, 1 ireduce, 2 ireduce_scatter_block"""
+    k = rt().mi355x_nbc_decision(coll, n, nbytes, 1 if inplace else 0)
+    check(0 if k >= 0 else k, "mi355x_nbc_decision")
+    return k
+
+
+def nbc_ring_block(count: int, n: int, e: int) -> tuple[int, int]:
+    """(offset, length) in elements of segment e of coll/libnbc's ring partition"""
+    off, ln = ctypes.c_size_t(), ctypes.c_size_t()
+    check(rt().mi355x_nbc_ring_block(count, n, e, ctypes.byref(off), ctypes.byref(ln)), "mi355x_nbc_ring_block")
+    return off.value, ln.value
 
 
 def env_flag(name: str, default: str = "") -> str:

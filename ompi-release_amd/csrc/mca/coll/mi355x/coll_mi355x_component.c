@@ -333,6 +333,7 @@ unsigned long long mca_coll_mi355x_svc_copy_max = 1ull << 20;
 int mca_coll_mi355x_svc_idle_us = 1000;
 int mca_coll_mi355x_svc_shrink_us = 100;
 int mca_coll_mi355x_selftest = 1;
+int mca_coll_mi355x_nb_order = 0;
 int mca_coll_mi355x_timeout_s = 0;  /* 0: the engine's own (MI355X_TIMEOUT_S, else one day) */
 
 /* 1: the call runs in the engine (a rank with host buffers joins on device copies); 0: it runs in
@@ -1460,6 +1461,11 @@ static int nb_host_join(mca_coll_mi355x_module_t *m, void *sbuf, void *rbuf, int
         return nb_staged_start(comm, request, st_, in_, rc_);                                     \
     } while (0)
 
+/* a libnbc-ordered post (coll_mi355x_nb_order = 1) whose program the device cannot hold: every rank
+ * gets this answer (it depends on the sizes only) and takes the staged path to the lower-priority
+ * component -- libnbc itself */
+#define NB_UNFIT(RC) ((RC) == MI355X_ERR_UNSUPPORTED && mca_coll_mi355x_nb_order != 0)
+
 int mca_coll_mi355x_iallreduce(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
                                struct ompi_communicator_t *comm, ompi_request_t **request,
                                mca_coll_base_module_t *module)
@@ -1480,14 +1486,15 @@ int mca_coll_mi355x_iallreduce(void *sbuf, void *rbuf, int count, struct ompi_da
         void *sd, *rd;
         int rc = nb_host_join(m, sbuf, rbuf, inplace, bytes, bytes, 1, &sd, &rd, &st);
         if (rc == MI355X_SUCCESS) rc = mi355x_iallreduce(m->engine, sd, rd, (size_t)count, t, op->o_f_to_c_index, NULL, &eng);
-        if (rc != MI355X_SUCCESS) {
-            nb_stage_release(&st);
-            return map_rc(rc);
-        }
-        return nb_start_full(eng, comm, request, 0, &st);
+        if (rc == MI355X_SUCCESS) return nb_start_full(eng, comm, request, 0, &st);
+        nb_stage_release(&st);
+        if (!NB_UNFIT(rc)) return map_rc(rc);
+    } else {
+        int rc = mi355x_iallreduce(m->engine, inplace ? NULL : sbuf, rbuf, (size_t)count, t, op->o_f_to_c_index, NULL, &eng);
+        if (!NB_UNFIT(rc)) return rc ? map_rc(rc) : nb_start(eng, comm, request);
     }
-    int rc = mi355x_iallreduce(m->engine, inplace ? NULL : sbuf, rbuf, (size_t)count, t, op->o_f_to_c_index, NULL, &eng);
-    return rc ? map_rc(rc) : nb_start(eng, comm, request);
+    const size_t span = dt_span(dtype, (size_t)count);
+    NB_STAGED(iallreduce, span, span, inplace, span, dtype, sbuf, rbuf, count, dtype, op, comm);
 }
 
 int mca_coll_mi355x_ireduce(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
@@ -1513,15 +1520,17 @@ int mca_coll_mi355x_ireduce(void *sbuf, void *rbuf, int count, struct ompi_datat
         int rc = nb_host_join(m, sbuf, rbuf, inplace, bytes, bytes, me == root, &sd, &rd, &st);
         if (rc == MI355X_SUCCESS)
             rc = mi355x_ireduce(m->engine, sd, rd, (size_t)count, t, op->o_f_to_c_index, root, NULL, &eng);
-        if (rc != MI355X_SUCCESS) {
-            nb_stage_release(&st);
-            return map_rc(rc);
-        }
-        return nb_start_full(eng, comm, request, 0, &st);
+        if (rc == MI355X_SUCCESS) return nb_start_full(eng, comm, request, 0, &st);
+        nb_stage_release(&st);
+        if (!NB_UNFIT(rc)) return map_rc(rc);
+    } else {
+        int rc = mi355x_ireduce(m->engine, inplace ? NULL : sbuf, me == root ? rbuf : NULL, (size_t)count, t,
+                                op->o_f_to_c_index, root, NULL, &eng);
+        if (!NB_UNFIT(rc)) return rc ? map_rc(rc) : nb_start(eng, comm, request);
     }
-    int rc = mi355x_ireduce(m->engine, inplace ? NULL : sbuf, me == root ? rbuf : NULL, (size_t)count, t,
-                            op->o_f_to_c_index, root, NULL, &eng);
-    return rc ? map_rc(rc) : nb_start(eng, comm, request);
+    const size_t span = dt_span(dtype, (size_t)count);
+    if (me != root) rbuf = NULL;  /* not significant off the root: never staged */
+    NB_STAGED(ireduce, span, span, inplace, span, dtype, sbuf, rbuf, count, dtype, op, root, comm);
 }
 
 int mca_coll_mi355x_ireduce_scatter_block(void *sbuf, void *rbuf, int rcount, struct ompi_datatype_t *dtype,
@@ -1547,15 +1556,17 @@ int mca_coll_mi355x_ireduce_scatter_block(void *sbuf, void *rbuf, int rcount, st
         int rc = nb_host_join(m, sbuf, rbuf, inplace, in, out, 1, &sd, &rd, &st);
         if (rc == MI355X_SUCCESS)
             rc = mi355x_ireduce_scatter_block(m->engine, sd, rd, (size_t)rcount, t, op->o_f_to_c_index, NULL, &eng);
-        if (rc != MI355X_SUCCESS) {
-            nb_stage_release(&st);
-            return map_rc(rc);
-        }
-        return nb_start_full(eng, comm, request, 0, &st);
+        if (rc == MI355X_SUCCESS) return nb_start_full(eng, comm, request, 0, &st);
+        nb_stage_release(&st);
+        if (!NB_UNFIT(rc)) return map_rc(rc);
+    } else {
+        int rc = mi355x_ireduce_scatter_block(m->engine, inplace ? NULL : sbuf, rbuf, (size_t)rcount, t,
+                                              op->o_f_to_c_index, NULL, &eng);
+        if (!NB_UNFIT(rc)) return rc ? map_rc(rc) : nb_start(eng, comm, request);
     }
-    int rc = mi355x_ireduce_scatter_block(m->engine, inplace ? NULL : sbuf, rbuf, (size_t)rcount, t,
-                                          op->o_f_to_c_index, NULL, &eng);
-    return rc ? map_rc(rc) : nb_start(eng, comm, request);
+    const size_t in = dt_span(dtype, (size_t)rcount * (size_t)mi355x_comm_size_of(comm));
+    const size_t out = dt_span(dtype, (size_t)rcount);
+    NB_STAGED(ireduce_scatter_block, in, inplace ? in : out, inplace, out, dtype, sbuf, rbuf, rcount, dtype, op, comm);
 }
 
 /* the (count, dt) side of a staged nonblocking move: pack it into `p` now (local work), or set up
@@ -2146,6 +2157,7 @@ static int apply_engine_params(mca_coll_mi355x_module_t *m, struct ompi_communic
     int rc = OMPI_SUCCESS;
 #define KNOB(K, V, NAME) if (rc == OMPI_SUCCESS) rc = set_knob(m, MI355X_KNOB_##K, (long)(V), NAME)
     KNOB(SELFTEST, mca_coll_mi355x_selftest != 0, "selftest");
+    KNOB(NB_ORDER, mca_coll_mi355x_nb_order != 0, "nb_order");
     KNOB(PIPE, mca_coll_mi355x_pipe_min_ranks > 0 && n >= mca_coll_mi355x_pipe_min_ranks, "pipe_min_ranks");
     KNOB(PIPE_CHUNK_KIB, mca_coll_mi355x_pipe_chunk_kib, "pipe_chunk_kib");
     KNOB(PIPE_WG_PER_CU, mca_coll_mi355x_pipe_wg_per_cu, "pipe_wg_per_cu");
@@ -2303,6 +2315,10 @@ static int component_register(void)
     register_int("selftest", "Run the cross-device flows' self-tests at a communicator's first device-buffer collective "
                  "(a flow that fails on any rank is turned off on every rank); 0 = trust every flow", OPAL_INFO_LVL_9,
                  &mca_coll_mi355x_selftest);
+    register_int("nb_order", "Operand order of MPI_Iallreduce / MPI_Ireduce / MPI_Ireduce_scatter_block in the engine: "
+                 "0 = coll/tuned's, as the blocking calls; 1 = coll/libnbc's, the component that serves them otherwise "
+                 "(a libnbc tree the device cannot hold goes to that component)", OPAL_INFO_LVL_6,
+                 &mca_coll_mi355x_nb_order);
     register_int("timeout_s", "Bound of every wait of the engine, seconds (0 = the engine's own: MI355X_TIMEOUT_S, "
                  "else one day -- MPI's waits are unbounded; a rank whose process is gone is noticed without it)",
                  OPAL_INFO_LVL_9, &mca_coll_mi355x_timeout_s);

@@ -183,6 +183,7 @@ int mi355x_comm_create(const char *key, int rank, int size, int device, mi355x_c
     // behind at n = 2 in the one-GPU rehearsal (profiles/r02_bench_n{2,4,8}_*); MI355X_PIPE=0/1 decides
     c->pipe_on = env_double("MI355X_PIPE", size >= 4 ? 1.0 : 0.0) != 0.0;
     c->one_phase_max = (size_t)std::max(0.0, env_double("MI355X_ONE_PHASE_MAX_BYTES", (double)c->one_phase_max));
+    c->nb_order = env_double("MI355X_NB_ORDER", 0.0) != 0.0 ? 1 : 0;
     c->lat_on = env_double("MI355X_LAT_PROFILE", 0.0) != 0.0;
     c->rcache_max_maps = (size_t)std::max(0.0, env_double("MI355X_RCACHE_MAX_MAPS", 0.0));
     c->rcache_limit = (size_t)std::max(0.0, env_double("MI355X_RCACHE_SIZE_LIMIT", 0.0));
@@ -216,6 +217,7 @@ int mi355x_comm_create_loopback(int size, int device, mi355x_comm_t **comms)
         c->loopback = true;
         c->loop = shared;
         c->timeout_s = env_double("MI355X_TIMEOUT_S", kDefaultTimeoutS);
+        c->nb_order = env_double("MI355X_NB_ORDER", 0.0) != 0.0 ? 1 : 0;
         shared->refs++;
         comms[r] = c;
     }
@@ -477,6 +479,7 @@ int mi355x_comm_get(const mi355x_comm_t *c, int knob, long *value)
         break;
     }
     case MI355X_KNOB_RCACHE_EVICTIONS: *value = (long)c->rcache_evictions; break;
+    case MI355X_KNOB_NB_ORDER: *value = c->nb_order; break;
     default: return set_error(MI355X_ERR_ARG, "unknown knob %d", knob);
     }
     return MI355X_SUCCESS;
@@ -599,6 +602,14 @@ int mi355x_comm_set(mi355x_comm_t *c, int knob, long value)
             if (c->svc_ok && c->svcq) svc_park(c);
         }
         break;
+    case MI355X_KNOB_NB_ORDER: {
+        if (value != 0 && value != 1) return set_error(MI355X_ERR_ARG, "nb_order is 0 (coll/tuned) or 1 (coll/libnbc)");
+        // a posted call has read the order already on this rank and may not have on a peer
+        std::lock_guard<std::mutex> g(c->q_mtx);
+        if (c->pending) return set_error(MI355X_ERR_ARG, "nb_order may change only while no nonblocking call is pending");
+        c->nb_order = (int)value;
+        break;
+    }
     case MI355X_KNOB_STAGE_BYTES:
         if (value < 4096 || value >= (1l << 31)) return set_error(MI355X_ERR_ARG, "stage_bytes out of range");
         if (c->stage) (void)hipFree(c->stage);
@@ -617,6 +628,10 @@ int mi355x_comm_set(mi355x_comm_t *c, int knob, long value)
 //                    1/2 = reduce-to-0 with reduce algorithm `block` (1..5) + bcast)
 // kind 2: reduce to rank `block` with reduce algorithm `alg`;  kind 3: reduce_scatter ring block;
 // kind 4: reduce_scatter recursive halving block; kind 5: reduce chain to 0 with fan-out `block`.
+// coll/libnbc's programs (coll_nbc.cpp), every step the 3-buff rule op3(in1 = out, in2 = in) -- the
+// layouts above with 2 added to the first int ([3, ...] fold, [2, ...] tree):
+// kind 6: iallreduce (alg 101 binomial, 102 ring segment `block`); kind 7: ireduce to rank `block`
+// (alg 101 binomial, 103 chain); kind 8: ireduce_scatter_block.
 // Returns the number of ints written or < 0.
 int mi355x_sched_program(int kind, int n, int alg, int block, int *out, int cap)
 {
@@ -638,6 +653,14 @@ int mi355x_sched_program(int kind, int n, int alg, int block, int *out, int cap)
         ok = compile_expr(ep, roots[block], n, &pr);
         break;
     }
+    case 6:
+    case 7:
+    case 8:
+        if (block < 0 || block >= n) return set_error(MI355X_ERR_ARG, "bad block %d", block);
+        if (kind == 8) alg = NBC_BINOMIAL;
+        if (alg != NBC_BINOMIAL && alg != (kind == 6 ? NBC_RING : NBC_CHAIN)) return set_error(MI355X_ERR_ARG, "bad algorithm %d", alg);
+        ok = nbc_program(kind - 6, n, alg, block, &pr);
+        break;
     default: return set_error(MI355X_ERR_ARG, "unknown kind %d", kind);
     }
     if (!ok) return set_error(MI355X_ERR_UNSUPPORTED, "schedule does not compile");
@@ -654,6 +677,7 @@ int mi355x_sched_program(int kind, int n, int alg, int block, int *out, int cap)
             v.push_back(t.in);
         }
     }
+    if (pr.three) v[0] += 2;
     if ((int)v.size() > cap) return set_error(MI355X_ERR_ARG, "cap too small");
     for (size_t i = 0; i < v.size(); ++i) out[i] = v[i];
     return (int)v.size();

@@ -148,10 +148,13 @@ struct GfSeg {
 int gather_fold(mi355x_comm *c, const void *in, size_t count, int type, int op, const std::vector<GfSeg> &segs,
                 hipStream_t s);
 void gfold_idle(mi355x_comm *c, hipStream_t s);
-int gfold_allreduce(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, hipStream_t s);
-int gfold_reduce(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, int root, hipStream_t s);
+// (nbc: coll/libnbc's selection and programs, coll_nbc.cpp)
+int gfold_allreduce(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, hipStream_t s,
+                    bool nbc = false);
+int gfold_reduce(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, int root, hipStream_t s,
+                 bool nbc = false);
 int gfold_reduce_scatter_block(mi355x_comm *c, const void *in, void *rbuf, size_t rcount, int type, int op,
-                               hipStream_t s);
+                               hipStream_t s, bool nbc = false);
 int gfold_reduce_scatter(mi355x_comm *c, const void *in, void *rbuf, const size_t *disp, int type, int op,
                          hipStream_t s);
 int gfold_scan(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, int last, hipStream_t s);
@@ -182,10 +185,20 @@ void worker_main(mi355x_comm *c);
 int post(mi355x_comm *c, void *stream, std::function<int(hipStream_t)> run, mi355x_request **out);
 int allreduce_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type, int op,
                      void *stream);
+// nbc: coll/libnbc's selection and programs (the nonblocking calls under MI355X_KNOB_NB_ORDER = 1);
+// such a call takes the host-synchronised flows only (no LL, resident-service or pipelined kernel)
 int reduce_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type, int op, int root,
-                  void *stream);
+                  void *stream, bool nbc = false);
 int reduce_scatter_block_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t rcount, int type,
-                                int op, void *stream);
+                                int op, void *stream, bool nbc = false);
+// coll_nbc.cpp
+int nbc_allreduce_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type, int op,
+                       void *stream);
+// the reduce (root >= 0) or reduce_scatter_block (root < 0) program of libnbc for the call
+bool nbc_reduce_program(const mi355x_comm *c, size_t count, size_t esz, int root, Program *pr, int *alg);
+// MI355X_SUCCESS, or MI355X_ERR_UNSUPPORTED when the call's libnbc program does not fit the device
+// (coll: 0 iallreduce, 1 ireduce, 2 ireduce_scatter_block; count = the whole vector's elements)
+int nbc_check(const mi355x_comm *c, int coll, size_t count, int type, bool inplace, int root);
 int reduce_scatter_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, const int *rcounts, int type,
                           int op, void *stream);
 int allgather_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, void *stream);

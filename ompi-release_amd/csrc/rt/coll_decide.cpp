@@ -135,6 +135,10 @@ double env_double(const char *name, double dflt)
 void drain(mi355x_comm *c)
 {
     std::unique_lock<std::mutex> g(c->q_mtx);
+    // the progress thread is inside a posted call (pending >= 1) and would wait for itself: the
+    // device setup of a communicator whose first device-buffer collective is a nonblocking one
+    // applies the preset service limits through mi355x_comm_set, which drains
+    if (c->worker.joinable() && c->worker.get_id() == std::this_thread::get_id()) return;
     c->q_cv.wait(g, [c] { return c->pending == 0; });
 }
 

@@ -265,8 +265,10 @@ int allreduce_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count,
 //   large  : owner-computes -- rank r evaluates ring block r from the n inputs into its own
 //            memory, then the root pulls the blocks (each link carries 2 S/n, writes stay local);
 //   staged : (allocations >= ipc_max) the root evaluates everything through the staging buffers.
+// nbc: coll/libnbc's selection and 3-buff programs instead (MPI_Ireduce under NB_ORDER = 1,
+// coll_nbc.cpp), through the same flows less the LL one.
 int reduce_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type, int op, int root,
-                  void *stream)
+                  void *stream, bool nbc)
 {
     int rc = check_common(c, op, type);
     if (rc) return rc;
@@ -277,24 +279,25 @@ int reduce_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count, in
     CallStream call_stream(c, s);  // (the setup work of this call, if any, runs on its stream)
     if (const int rs_ = dev_setup(c)) return rs_;  // (first device-buffer collective: collective setup)
     if (!coll_slot_supported(op, type)) {  // (no fold kernel carries the slot: gather-then-fold, coll_gfold.cpp)
-        return gfold_reduce(c, sbuf ? sbuf : rbuf, rbuf, count, type, op, root, s);
+        return gfold_reduce(c, sbuf ? sbuf : rbuf, rbuf, count, type, op, root, s, nbc);
     }
     const size_t esz = mi355x_type_size(type);
     const void *in = sbuf ? sbuf : rbuf;
     const bool am_root = (c->rank == root);
     if (c->size == 1) {
-        c->last_alg = RED_LINEAR;
+        c->last_alg = nbc ? nbc_ireduce_decision(1, count, esz) : (int)RED_LINEAR;
         if (sbuf && sbuf != rbuf) MI_HIP(hipMemcpyAsync(rbuf, sbuf, count * esz, hipMemcpyDeviceToDevice, s));
         MI_HIP(hipStreamSynchronize(s));
         return MI355X_SUCCESS;
     }
     Program pr;
     int ra;
-    if (!reduce_program(c, count, esz, root, &pr, &ra)) return set_error(MI355X_ERR_UNSUPPORTED, "schedule too large");
+    if (!(nbc ? nbc_reduce_program(c, count, esz, root, &pr, &ra) : reduce_program(c, count, esz, root, &pr, &ra)))
+        return set_error(MI355X_ERR_UNSUPPORTED, "schedule too large");
     c->last_alg = ra;
-    rc = svc_maybe_claim(c, count * esz <= c->svc_max);
+    rc = svc_maybe_claim(c, !nbc && count * esz <= c->svc_max);
     if (rc) return rc;
-    if (ll_usable(c, count * esz) && (pr.is_fold || c->size <= kTreeMax)) {
+    if (!nbc && ll_usable(c, count * esz) && (pr.is_fold || c->size <= kTreeMax)) {
         LLArgs a;
         std::memset(&a, 0, sizeof(a));
         a.mode = LL_RED;
@@ -315,7 +318,7 @@ int reduce_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count, in
     }
     MI_HIP(hipStreamSynchronize(s));
     const void *mine[2] = {in, am_root ? nullptr : c->scratch};
-    const uint64_t sig[4] = {6, count, ((uint64_t)type << 32) | (uint64_t)op, (uint64_t)root};
+    const uint64_t sig[4] = {nbc ? 106u : 6u, count, ((uint64_t)type << 32) | (uint64_t)op, (uint64_t)root};
     std::vector<std::vector<void *>> P;
     bool staged = false;
     rc = exchange(c, 2, mine, sig, P, &staged);
@@ -366,8 +369,10 @@ int reduce_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count, in
 
 // MPI_Reduce_scatter_block as coll/basic runs it: tuned reduce to 0 + scatter
 // (coll_basic_reduce_scatter_block.c:54-111); sbuf NULL = MPI_IN_PLACE (input in rbuf).
+// nbc: coll/libnbc's binomial reduce to rank 0 + scatter instead (MPI_Ireduce_scatter_block under
+// NB_ORDER = 1, coll_libnbc_ireduce_scatter_block.c:78-138), never through the resident service.
 int reduce_scatter_block_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t rcount, int type,
-                                int op, void *stream)
+                                int op, void *stream, bool nbc)
 {
     int rc = check_common(c, op, type);
     if (rc) return rc;
@@ -377,16 +382,17 @@ int reduce_scatter_block_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, si
     CallStream call_stream(c, s);  // (the setup work of this call, if any, runs on its stream)
     if (const int rs_ = dev_setup(c)) return rs_;  // (first device-buffer collective: collective setup)
     if (!coll_slot_supported(op, type)) {  // (no fold kernel carries the slot: gather-then-fold, coll_gfold.cpp)
-        return gfold_reduce_scatter_block(c, sbuf ? sbuf : rbuf, rbuf, rcount, type, op, s);
+        return gfold_reduce_scatter_block(c, sbuf ? sbuf : rbuf, rbuf, rcount, type, op, s, nbc);
     }
     const size_t esz = mi355x_type_size(type);
     const void *in = sbuf ? sbuf : rbuf;
     Program pr;
     int ra;
-    if (!reduce_program(c, count, esz, 0, &pr, &ra)) return set_error(MI355X_ERR_UNSUPPORTED, "schedule too large");
+    if (!(nbc ? nbc_reduce_program(c, count, esz, -1, &pr, &ra) : reduce_program(c, count, esz, 0, &pr, &ra)))
+        return set_error(MI355X_ERR_UNSUPPORTED, "schedule too large");
     c->last_alg = ra;
     const bool inplace = (in == (const void *)rbuf);
-    rc = svc_maybe_claim(c, !inplace && c->svc_rs && rcount * esz <= c->svc_pull_max);
+    rc = svc_maybe_claim(c, !nbc && !inplace && c->svc_rs && rcount * esz <= c->svc_pull_max);
     if (rc) return rc;
     if (inplace) {
         rc = ensure_scratch(c, rcount * esz);
@@ -394,10 +400,10 @@ int reduce_scatter_block_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, si
     }
     MI_HIP(hipStreamSynchronize(s));
     const void *mine[1] = {in};
-    const uint64_t sig[4] = {2, rcount, (uint64_t)type, (uint64_t)op};
+    const uint64_t sig[4] = {nbc ? 102u : 2u, rcount, (uint64_t)type, (uint64_t)op};
     std::vector<std::vector<void *>> P;
     bool staged = false;
-    const bool pull_cand = !inplace && svc_rs_usable(c, rcount * esz, pr);  // the resident service evaluates
+    const bool pull_cand = !nbc && !inplace && svc_rs_usable(c, rcount * esz, pr);  // the resident service evaluates
     c->svc_keep = pull_cand;
     rc = exchange(c, 1, mine, sig, P, &staged);
     c->svc_keep = false;
@@ -737,6 +743,10 @@ int mi355x_iallreduce(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t cou
 {
     int rc = check_common(c, op, type);
     if (rc) return rc;
+    if (c->nb_order) {  // coll/libnbc's order (coll_nbc.cpp); a program that does not fit fails the post
+        if ((rc = nbc_check(c, 0, count, type, !sbuf || sbuf == rbuf, 0))) return rc;
+        return post(c, stream, [=](hipStream_t s) { return nbc_allreduce_impl(c, sbuf, rbuf, count, type, op, s); }, req);
+    }
     return post(c, stream, [=](hipStream_t s) { return allreduce_impl(c, sbuf, rbuf, count, type, op, s); }, req);
 }
 int mi355x_ireduce(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type, int op, int root,
@@ -745,15 +755,19 @@ int mi355x_ireduce(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count,
     int rc = check_common(c, op, type);
     if (rc) return rc;
     if (root < 0 || root >= c->size) return set_error(MI355X_ERR_ARG, "bad root");
-    return post(c, stream, [=](hipStream_t s) { return reduce_impl(c, sbuf, rbuf, count, type, op, root, s); }, req);
+    const bool nbc = c->nb_order != 0;
+    if (nbc && (rc = nbc_check(c, 1, count, type, false, root))) return rc;
+    return post(c, stream, [=](hipStream_t s) { return reduce_impl(c, sbuf, rbuf, count, type, op, root, s, nbc); }, req);
 }
 int mi355x_ireduce_scatter_block(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t rcount, int type, int op,
                                  void *stream, mi355x_request_t **req)
 {
     int rc = check_common(c, op, type);
     if (rc) return rc;
+    const bool nbc = c->nb_order != 0;
+    if (nbc && (rc = nbc_check(c, 2, rcount * (size_t)c->size, type, false, 0))) return rc;
     return post(c, stream,
-                [=](hipStream_t s) { return reduce_scatter_block_impl(c, sbuf, rbuf, rcount, type, op, s); }, req);
+                [=](hipStream_t s) { return reduce_scatter_block_impl(c, sbuf, rbuf, rcount, type, op, s, nbc); }, req);
 }
 int mi355x_iallgather(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, void *stream,
                       mi355x_request_t **req)

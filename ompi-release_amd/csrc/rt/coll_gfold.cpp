@@ -58,6 +58,17 @@ double now_s()
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// one program node: out = op2(out, in), or for coll/libnbc's programs out = op3(in1 = out, in2 = in).
+// The 3-buff target is its own in1: op/hip's kernels are elementwise -- a lane (for the 32-byte
+// types the two lanes of an element, which swap halves in registers) loads every operand byte of
+// the elements it stores before it stores them, and stores nothing else -- so a target that is
+// exactly one operand is safe, as the 2-buff form (target = its inout operand) already relies on.
+int step(const Program &pr, int op, int type, char *out, const char *in, size_t len, hipStream_t s)
+{
+    if (pr.three) return mi355x_op_reduce_3buff(op, type, out, in, out, len, s);
+    return mi355x_op_reduce(op, type, in, out, len, s);
+}
+
 // one program evaluated over `len` elements of the gathered window: blk(q) = rank q's elements
 int eval_program(const Program &pr, int op, int type, char *g, size_t wbytes, size_t lo_bytes, size_t len,
                  char *dst, hipStream_t s)
@@ -71,16 +82,16 @@ int eval_program(const Program &pr, int op, int type, char *g, size_t wbytes, si
         for (size_t j = 1; j < pr.order.size(); ++j) {
             char *x = blk(pr.order[j]);
             if ((pr.role_mask >> j) & 1) {  // op2(out = acc, in = x)
-                if ((rc = mi355x_op_reduce(op, type, x, acc, len, s))) return rc;
+                if ((rc = step(pr, op, type, acc, x, len, s))) return rc;
             } else {                        // op2(out = x, in = acc)
-                if ((rc = mi355x_op_reduce(op, type, acc, x, len, s))) return rc;
+                if ((rc = step(pr, op, type, x, acc, len, s))) return rc;
                 acc = x;
             }
         }
         res = acc;
     } else {
         for (const TreeStep &st : pr.steps)  // R[dst = out] = op2(out = R[out], in = R[in])
-            if ((rc = mi355x_op_reduce(op, type, blk(st.in), blk(st.out), len, s))) return rc;
+            if ((rc = step(pr, op, type, blk(st.out), blk(st.in), len, s))) return rc;
         res = blk(pr.result);
     }
     if (dst) MI_HIP(hipMemcpyAsync(dst, res, len * esz, hipMemcpyDeviceToDevice, s));
@@ -147,9 +158,27 @@ int gather_fold(mi355x_comm *c, const void *in, size_t count, int type, int op, 
 
 // ---- the collectives' segments -------------------------------------------------------------------
 
-int gfold_allreduce(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, hipStream_t s)
+int gfold_allreduce(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, hipStream_t s,
+                    bool nbc)
 {
     const size_t esz = mi355x_type_size(type);
+    if (nbc) {  // coll/libnbc: the binomial tree for every element, or the ring's segments (coll_nbc.cpp)
+        const int nalg = nbc_iallreduce_decision(c->size, count, esz, in == (const void *)rbuf);
+        c->last_alg = nalg;
+        std::vector<GfSeg> nsegs;
+        for (int b = 0; b < (nalg == NBC_RING ? c->size : 1); ++b) {
+            GfSeg sg;
+            sg.e0 = 0;
+            sg.ne = count;
+            if (nalg == NBC_RING) nbc_ring_block(count, c->size, b, &sg.e0, &sg.ne);
+            if (!nbc_program(0, c->size, nalg, b, &sg.pr)) return set_error(MI355X_ERR_UNSUPPORTED, "schedule too large");
+            sg.dst = static_cast<char *>(rbuf) + sg.e0 * esz;
+            if (sg.ne) nsegs.push_back(sg);
+        }
+        const int rc = gather_fold(c, in, count, type, op, nsegs, s);
+        c->last_alg = nalg;  // (the gather's own allgather calls report theirs)
+        return rc;
+    }
     int alg = pick_allreduce(c, count, esz);
     // the reference's fallbacks (coll_tuned_allreduce.c:672-679, :398-405), as allreduce_impl
     if (alg == AR_RING_SEGMENTED && count < (size_t)c->size * computed_segcount(1u << 20, esz, count)) alg = AR_RING;
@@ -175,12 +204,14 @@ int gfold_allreduce(mi355x_comm *c, const void *in, void *rbuf, size_t count, in
     return gather_fold(c, in, count, type, op, segs, s);
 }
 
-int gfold_reduce(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, int root, hipStream_t s)
+int gfold_reduce(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, int root, hipStream_t s,
+                 bool nbc)
 {
     const size_t esz = mi355x_type_size(type);
     GfSeg sg;
     int ra;
-    if (!reduce_program(c, count, esz, root, &sg.pr, &ra)) return set_error(MI355X_ERR_UNSUPPORTED, "schedule too large");
+    if (!(nbc ? nbc_reduce_program(c, count, esz, root, &sg.pr, &ra) : reduce_program(c, count, esz, root, &sg.pr, &ra)))
+        return set_error(MI355X_ERR_UNSUPPORTED, "schedule too large");
     c->last_alg = ra;
     std::vector<GfSeg> segs;
     if (c->rank == root) {
@@ -189,23 +220,28 @@ int gfold_reduce(mi355x_comm *c, const void *in, void *rbuf, size_t count, int t
         sg.dst = static_cast<char *>(rbuf);
         segs.push_back(sg);
     }
-    return gather_fold(c, in, count, type, op, segs, s);
+    const int rc = gather_fold(c, in, count, type, op, segs, s);
+    if (nbc) c->last_alg = ra;  // (the gather's own allgather calls report theirs)
+    return rc;
 }
 
 int gfold_reduce_scatter_block(mi355x_comm *c, const void *in, void *rbuf, size_t rcount, int type, int op,
-                               hipStream_t s)
+                               hipStream_t s, bool nbc)
 {
     // coll/basic: the tuned reduce of the whole vector to rank 0, then a scatter
     // (coll_basic_reduce_scatter_block.c:54-111)
     const size_t count = rcount * (size_t)c->size, esz = mi355x_type_size(type);
     GfSeg sg;
     int ra;
-    if (!reduce_program(c, count, esz, 0, &sg.pr, &ra)) return set_error(MI355X_ERR_UNSUPPORTED, "schedule too large");
+    if (!(nbc ? nbc_reduce_program(c, count, esz, -1, &sg.pr, &ra) : reduce_program(c, count, esz, 0, &sg.pr, &ra)))
+        return set_error(MI355X_ERR_UNSUPPORTED, "schedule too large");
     c->last_alg = ra;
     sg.e0 = (size_t)c->rank * rcount;
     sg.ne = rcount;
     sg.dst = static_cast<char *>(rbuf);
-    return gather_fold(c, in, count, type, op, std::vector<GfSeg>(1, sg), s);
+    const int rc = gather_fold(c, in, count, type, op, std::vector<GfSeg>(1, sg), s);
+    if (nbc) c->last_alg = ra;
+    return rc;
 }
 
 int gfold_reduce_scatter(mi355x_comm *c, const void *in, void *rbuf, const size_t *disp, int type, int op,

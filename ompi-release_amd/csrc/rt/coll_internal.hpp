@@ -14,6 +14,7 @@ constexpr int kTreeMax = 16;    // register-program width of k_tree
 constexpr int kTreeSteps = 64;
 
 // k_fold: acc = x[order[0]]; acc = role_j ? op2(acc, x[order[j]]) : op2(x[order[j]], acc)
+// (three: op3(in1, in2) in place of op2(out, in) -- coll/libnbc's programs, Program::three)
 struct FoldArgs {
     const void *src[kMaxRanks];  // rank inputs, already offset to this launch's first element
     void *dst[kMaxRanks];        // destinations, same offset
@@ -23,6 +24,7 @@ struct FoldArgs {
     int nd;                      // destinations written
     size_t n;                    // elements
     size_t head, nvec;           // filled by the launcher
+    int three;
 };
 
 struct TreeStep {
@@ -36,6 +38,7 @@ struct TreeArgs {
     TreeStep steps[kTreeSteps];
     int nsteps, nr, nd, result;
     size_t n;
+    int three;                   // R[dst] = op3(in1 = R[out], in2 = R[in])
 };
 
 // k_ring_all: the ring allreduce's per-element order over the WHOLE vector in one launch -- element
@@ -46,6 +49,10 @@ struct RingAllArgs {
     void *dst;                   // my rbuf
     int n;
     uint32_t count, early, late, split;  // elements; the first `split` blocks hold `early` elements
+    // coll/libnbc's ring (allred_sched_ring): seg != 0 = its partition, segments of `seg` elements,
+    // and segment e folds x_{e-1}, x_e, ..., x_{e+n-2} (one rank earlier than the block of the same
+    // number above) under the 3-buff rule, own value as in1; 0: the order above
+    uint32_t seg;
 };
 
 // k_copy: bytes from one source to nd destinations

@@ -15,6 +15,9 @@
 //   k_tree  : a register program R[dst] = op2(out=R[o], in=R[i]) over <= 16 rank inputs --
 //             the recursive-doubling butterfly (:193-284), binomial / binary reduce trees.
 //   k_copy  : no arithmetic (allgather, bcast slices): one source, many destinations.
+// k_fold, k_tree and k_ring_all also have a 3-buff form (template parameter THREE: op3(in1, in2) in
+// place of op2(out, in)) for coll/libnbc's programs (Program::three, coll_nbc.cpp), and k_ring_all a
+// form over libnbc's ring partition; the op2 instantiations are the code they were without them.
 // Source/destination pointers arrive in the kernarg segment (uniform, scalar-loaded), so the
 // per-rank indirection costs no VGPRs.  Same alignment scheme as op_kernels.hip: if every
 // pointer shares the misalignment mod 16 a scalar head peels to the 16-B body, else the whole
@@ -65,28 +68,43 @@ template <bool NT, typename V> __device__ __forceinline__ void cstore_t(void *p,
     }
 }
 
+// ------------------------------------------------------------------ the two reduction rules
+// THREE: the 3-buff rule op3(in1 = o, in2 = a) of coll/libnbc's programs (Program::three) instead
+// of the 2-buff rule op2(out = o, in = a).  The two differ for the MAXLOC / MINLOC pairs only
+// (op_functors.hpp: a NaN value, the value kept on a tie), so only those slots instantiate the
+// THREE kernels; every other slot's op3 is its op2 and a `three` program runs the op2 kernels.
+template <class F> struct Op3Differs : std::false_type {};
+template <typename P, bool MAX> struct Op3Differs<OpLoc<P, MAX>> : std::true_type {};
+
+template <class F, bool THREE>
+__device__ __forceinline__ typename F::T rule(const typename F::T &o, const typename F::T &a)
+{
+    if constexpr (THREE) return F::op3(o, a);
+    else return F::op2(o, a);
+}
+
 // ------------------------------------------------------------------ fold
-template <class F>
+template <class F, bool THREE>
 __device__ __forceinline__ typename F::T fold_step(const typename F::T &acc, const typename F::T &x,
                                                    bool acc_is_out)
 {
-    return acc_is_out ? F::op2(acc, x) : F::op2(x, acc);
+    return acc_is_out ? rule<F, THREE>(acc, x) : rule<F, THREE>(x, acc);
 }
 
 // fold of element i (scalar path)
-template <class F>
+template <class F, bool THREE>
 __device__ __forceinline__ typename F::T fold_scalar(const FoldArgs &a, size_t i)
 {
     using T = typename F::T;
     T acc = static_cast<const T *>(a.src[a.order[0]])[i];
     for (int j = 1; j < a.nr; ++j) {
         const T x = static_cast<const T *>(a.src[a.order[j]])[i];
-        acc = fold_step<F>(acc, x, (a.role_mask >> j) & 1u);
+        acc = fold_step<F, THREE>(acc, x, (a.role_mask >> j) & 1u);
     }
     return acc;
 }
 
-template <class F, int U, bool NT>
+template <class F, int U, bool NT, bool THREE>
 __global__ __launch_bounds__(256) void k_fold(FoldArgs a)
 {
     using T = typename F::T;
@@ -96,7 +114,7 @@ __global__ __launch_bounds__(256) void k_fold(FoldArgs a)
     const size_t nthr = (size_t)gridDim.x * blockDim.x;
 
     for (size_t i = tid; i < a.head; i += nthr) {
-        const T r = fold_scalar<F>(a, i);
+        const T r = fold_scalar<F, THREE>(a, i);
         for (int d = 0; d < a.nd; ++d) static_cast<T *>(a.dst[d])[i] = r;
     }
 
@@ -127,7 +145,7 @@ __global__ __launch_bounds__(256) void k_fold(FoldArgs a)
 #pragma unroll
                     for (int u = 0; u < U; ++u)
 #pragma unroll
-                        for (int e = 0; e < EPV; ++e) acc[u].e[e] = fold_step<F>(acc[u].e[e], x[j][u].e[e], ao);
+                        for (int e = 0; e < EPV; ++e) acc[u].e[e] = fold_step<F, THREE>(acc[u].e[e], x[j][u].e[e], ao);
                 }
             }
         }
@@ -152,7 +170,7 @@ __global__ __launch_bounds__(256) void k_fold(FoldArgs a)
 #pragma unroll
                     for (int u = 0; u < U; ++u)
 #pragma unroll
-                        for (int e = 0; e < EPV; ++e) acc[u].e[e] = fold_step<F>(acc[u].e[e], x[j][u].e[e], ao);
+                        for (int e = 0; e < EPV; ++e) acc[u].e[e] = fold_step<F, THREE>(acc[u].e[e], x[j][u].e[e], ao);
                 }
             }
         }
@@ -168,7 +186,7 @@ __global__ __launch_bounds__(256) void k_fold(FoldArgs a)
 
     const size_t t0 = a.head + nvec * EPV;
     for (size_t i = t0 + tid; i < a.n; i += nthr) {
-        const T r = fold_scalar<F>(a, i);
+        const T r = fold_scalar<F, THREE>(a, i);
         for (int d = 0; d < a.nd; ++d) static_cast<T *>(a.dst[d])[i] = r;
     }
 }
@@ -176,12 +194,20 @@ __global__ __launch_bounds__(256) void k_fold(FoldArgs a)
 // ------------------------------------------------------------------ ring order, whole vector
 // Small ring-ordered messages: every rank evaluates every block (one element per lane, the n loads
 // issued before the fold), so the allreduce needs one launch and one host barrier instead of two.
-template <class F> __global__ __launch_bounds__(256) void k_ring_all(RingAllArgs a)
+// NBC: coll/libnbc's ring instead (RingAllArgs::seg): element i of segment e = i / seg folds from
+// rank e - 1 on; THREE as above.
+template <class F, bool NBC, bool THREE> __global__ __launch_bounds__(256) void k_ring_all(RingAllArgs a)
 {
     using T = typename F::T;
     const uint32_t se = a.split * a.early;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.count; i += gridDim.x * blockDim.x) {
-        const int b = (int)(i < se ? i / a.early : a.split + (i - se) / a.late);
+        int b;
+        if constexpr (NBC) {
+            const int e = (int)(i / a.seg);  // < n: seg = ceil(count / n)
+            b = e ? e - 1 : a.n - 1;
+        } else {
+            b = (int)(i < se ? i / a.early : a.split + (i - se) / a.late);
+        }
         T acc{};
         for (int j0 = 0; j0 < a.n; j0 += kFoldChunk) {  // up to 8 loads in flight, then fold them
             T x[kFoldChunk];
@@ -192,7 +218,7 @@ template <class F> __global__ __launch_bounds__(256) void k_ring_all(RingAllArgs
             }
 #pragma unroll
             for (int j = 0; j < kFoldChunk; ++j) {
-                if (j0 + j < a.n) acc = (j0 + j == 0) ? x[0] : F::op2(x[j], acc);
+                if (j0 + j < a.n) acc = (j0 + j == 0) ? x[0] : rule<F, THREE>(x[j], acc);
             }
         }
         static_cast<T *>(a.dst)[i] = acc;
@@ -210,7 +236,7 @@ __device__ __forceinline__ typename F::T pick(const typename F::T (&R)[kTreeMax]
     return v;
 }
 
-template <class F> __global__ __launch_bounds__(256) void k_tree(TreeArgs a)
+template <class F, bool THREE> __global__ __launch_bounds__(256) void k_tree(TreeArgs a)
 {
     using T = typename F::T;
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -222,7 +248,7 @@ template <class F> __global__ __launch_bounds__(256) void k_tree(TreeArgs a)
             if (s < a.nr) R[s] = static_cast<const T *>(a.src[s])[i];
         for (int k = 0; k < a.nsteps; ++k) {
             const TreeStep st = a.steps[k];
-            const T r = F::op2(pick<F>(R, st.out), pick<F>(R, st.in));
+            const T r = rule<F, THREE>(pick<F>(R, st.out), pick<F>(R, st.in));
 #pragma unroll
             for (int s = 0; s < kTreeMax; ++s)
                 if (s == st.dst) R[s] = r;
@@ -332,10 +358,19 @@ template <class F> static int launch_fold(FoldArgs a, hipStream_t s)
     const size_t scalar = a.n - a.nvec * EPV;
     if (scalar > work) work = scalar;
     const size_t blocks = grid_for(work, coll_tune().blocks_per_cu);
-    if ((size_t)(a.nr + a.nd) * a.n * sizeof(T) > ((size_t)256 << 20))
-        hipLaunchKernelGGL((k_fold<F, U, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((k_fold<F, U, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    const bool nt = (size_t)(a.nr + a.nd) * a.n * sizeof(T) > ((size_t)256 << 20);
+    bool three = false;
+    if constexpr (Op3Differs<F>::value) three = a.three != 0;
+    if (three) {
+        if constexpr (Op3Differs<F>::value) {
+            if (nt) hipLaunchKernelGGL((k_fold<F, U, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((k_fold<F, U, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        }
+    } else if (nt) {
+        hipLaunchKernelGGL((k_fold<F, U, true, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    } else {
+        hipLaunchKernelGGL((k_fold<F, U, false, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    }
     MI_HIP(hipGetLastError());
     return MI355X_SUCCESS;
 }
@@ -343,7 +378,13 @@ template <class F> static int launch_fold(FoldArgs a, hipStream_t s)
 template <class F> static int launch_ring_all(const RingAllArgs &a, hipStream_t s)
 {
     if (a.count == 0) return MI355X_SUCCESS;
-    hipLaunchKernelGGL((k_ring_all<F>), dim3((unsigned)grid_for(a.count, 8)), dim3(256), 0, s, a);
+    const dim3 grid((unsigned)grid_for(a.count, 8));
+    if (a.seg) {
+        if constexpr (Op3Differs<F>::value) hipLaunchKernelGGL((k_ring_all<F, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_ring_all<F, true, false>), grid, dim3(256), 0, s, a);
+    } else {
+        hipLaunchKernelGGL((k_ring_all<F, false, false>), grid, dim3(256), 0, s, a);
+    }
     MI_HIP(hipGetLastError());
     return MI355X_SUCCESS;
 }
@@ -352,7 +393,13 @@ template <class F> static int launch_tree(const TreeArgs &a, hipStream_t s)
 {
     if (a.n == 0) return MI355X_SUCCESS;
     const size_t blocks = grid_for(a.n, 4);
-    hipLaunchKernelGGL((k_tree<F>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    bool three = false;
+    if constexpr (Op3Differs<F>::value) three = a.three != 0;
+    if (three) {
+        if constexpr (Op3Differs<F>::value) hipLaunchKernelGGL((k_tree<F, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    } else {
+        hipLaunchKernelGGL((k_tree<F, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    }
     MI_HIP(hipGetLastError());
     return MI355X_SUCCESS;
 }

@@ -232,6 +232,7 @@ void ll_program(LLArgs &a, const Program &pr)
 // rank decides alike: the largest block, the program and the sizes are the same everywhere.
 bool svc_rs_usable(const mi355x_comm *c, size_t max_block_bytes, const Program &pr)
 {
+    if (pr.three) return false;  // (the service applies op2: a libnbc-ordered call is not taken)
     return c->svc_ok && c->svc_rs && (c->flows & MI355X_FLOW_SVC_RS) && !c->loopback && c->size >= 2 && c->size <= kLLMaxRanks && max_block_bytes <= c->svc_pull_max &&
            (pr.is_fold ? pr.order.size() == (size_t)c->size
                        : (c->size <= kTreeMax && pr.steps.size() <= (size_t)kTreeSteps));

@@ -39,6 +39,9 @@ struct Program {
     std::vector<TreeStep> steps;
     int result = 0;
     int nr = 0;                 // ranks referenced (inputs 0..nr-1)
+    // coll/libnbc's programs: every step is the 3-buff rule op3(in1 = the `out` slot, in2 = the
+    // `in` slot) (ompi_3buff_op_reduce, nbc.c:446-467) instead of op2
+    bool three = false;
 };
 
 // compile an expression tree rooted at `root` over ranks [0, n)
@@ -78,5 +81,27 @@ int reduce_scatter_decision(int n, size_t total_count, size_t dsize); // :456-50
 size_t computed_segcount(size_t segsize, size_t typelng, size_t count);
 // COLL_TUNED_COMPUTE_BLOCKCOUNT (coll_tuned.h:546-552) block offset/length
 void ring_block(size_t count, int n, int b, size_t *off, size_t *len);
+
+// ---- coll/libnbc (coll_nbc.cpp): the nonblocking reductions' own schedules -------------------
+// Every reduction step of libnbc is NBC_Sched_op(target, in1, in2) = ompi_3buff_op_reduce with the
+// rank's own data as in1 (nbc.c:123-145, :446-467); an op node (out, in) of these expressions is
+// op3(in1 = out, in2 = in) and the compiled Program carries three = true.
+enum NbcAlg { NBC_BINOMIAL = 101, NBC_RING = 102, NBC_CHAIN = 103 };
+int nbc_iallreduce_decision(int n, size_t count, size_t dsize, bool inplace);  // nbc_iallreduce.c:80-85
+int nbc_ireduce_decision(int n, size_t count, size_t dsize);                   // nbc_ireduce.c:74-88
+// binomial tree to `root`, rank 0 and the root swapped (RANK2VRANK; nbc_ireduce.c:211-285); with
+// root 0 also MPI_Iallreduce's tree (allred_sched_diss, nbc_iallreduce.c:225-272) and
+// MPI_Ireduce_scatter_block's (coll_libnbc_ireduce_scatter_block.c:78-116)
+int expr_nbc_binomial(ExprPool &p, int n, int root);
+int expr_nbc_reduce_chain(ExprPool &p, int n, int root);  // red_sched_chain, nbc_ireduce.c:288-340
+// ring (allred_sched_ring, nbc_iallreduce.c:304-471): segment e is folded x_{e-1}, x_e, ...,
+// x_{e+n-2}, every rank's own value as in1 and the received partial as in2
+Program nbc_ring_segment_program(int n, int e);
+// its partition (:311-329): segments of ceil(count / n), filled in order; the last non-empty one
+// is short, those after it empty
+void nbc_ring_block(size_t count, int n, int e, size_t *off, size_t *len);
+// the program of `alg` (NbcAlg) for MPI_Iallreduce (coll 0; block = ring segment), MPI_Ireduce
+// (coll 1; block = root) or MPI_Ireduce_scatter_block (coll 2); false: it does not fit the device
+bool nbc_program(int coll, int n, int alg, int block, Program *out);
 
 } // namespace mi355x

@@ -63,6 +63,7 @@ int run_program(int op, int type, const Program &pr, const std::vector<void *> &
         a.role_mask = pr.role_mask;
         a.nd = (int)dst.size();
         a.n = len;
+        a.three = pr.three ? 1 : 0;
         return launch_fold_slot(op, type, a, s);
     }
     if ((int)in.size() > kTreeMax) return set_error(MI355X_ERR_UNSUPPORTED, "tree program over > %d ranks", kTreeMax);
@@ -76,6 +77,7 @@ int run_program(int op, int type, const Program &pr, const std::vector<void *> &
     for (int k = 0; k < t.nsteps; ++k) t.steps[k] = pr.steps[k];
     t.result = pr.result;
     t.n = len;
+    t.three = pr.three ? 1 : 0;
     return launch_tree_slot(op, type, t, s);
 }
 

@@ -438,6 +438,9 @@ struct mi355x_comm {
     int knob_allreduce = 0, knob_reduce = 0, knob_rs = 0;
     int chain_fanout = mi355x::kDefaultChainFanout;
     const mi355x_rules_t *rules = nullptr;        // coll/tuned dynamic rules (not owned)
+    // MI355X_KNOB_NB_ORDER (env MI355X_NB_ORDER): 1 = iallreduce / ireduce / ireduce_scatter_block
+    // run coll/libnbc's selection and operand order (coll_nbc.cpp); 0 = coll/tuned's, as the blocking calls
+    int nb_order = 0;
     int last_alg = -1;
     double timeout_s = mi355x::kDefaultTimeoutS;
     bool time_phases = false;                     // MI355X_KNOB_TIME_PHASES
