@@ -5,7 +5,7 @@
  * coll/tuned (30) and coll/cuda (78) -- for intra-communicators whose ranks all live on this
  * node.  It provides allreduce, reduce, reduce_scatter, reduce_scatter_block, allgather, bcast,
  * gather(v), scatter(v), allgatherv, alltoall(v), scan and exscan, and the nonblocking iallreduce,
- * ireduce, ireduce_scatter_block, iallgather and ibcast; every other slot (alltoallw, barrier,
+ * ireduce, ireduce_scatter_block, iallgather, ibcast, iscan and iexscan; every other slot (alltoallw, barrier,
  * the other nonblocking and neighborhood ones) stays with the lower-priority modules.  Entry points have exactly the reference
  * signatures (coll.h:181-239) and replace, for device buffers:
  *   mca_coll_cuda_allreduce            (ompi/mca/coll/cuda/coll_cuda_allreduce.c:30-77)
@@ -47,6 +47,10 @@ int mca_coll_mi355x_reduce(void *sbuf, void *rbuf, int count, struct ompi_dataty
 int mca_coll_mi355x_iallreduce(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
                                struct ompi_communicator_t *comm, ompi_request_t **request,
                                mca_coll_base_module_t *module);
+int mca_coll_mi355x_iscan(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
+                          struct ompi_communicator_t *comm, ompi_request_t **request, mca_coll_base_module_t *module);
+int mca_coll_mi355x_iexscan(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
+                            struct ompi_communicator_t *comm, ompi_request_t **request, mca_coll_base_module_t *module);
 int mca_coll_mi355x_ireduce(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
                             int root, struct ompi_communicator_t *comm, ompi_request_t **request,
                             mca_coll_base_module_t *module);
@@ -155,6 +159,7 @@ extern int mca_coll_mi355x_svc_idle_us;                  /* 1000 */
 extern int mca_coll_mi355x_svc_shrink_us;                /* 100 */
 extern int mca_coll_mi355x_selftest;                     /* 1 */
 extern int mca_coll_mi355x_nb_order;                     /* 0: coll/tuned's order for the nonblocking reductions; 1: coll/libnbc's */
+extern unsigned long long mca_coll_mi355x_scan_part_min; /* bytes per rank from which scan / exscan take the partitioned flow; 0: never */
 /* the engine of a communicator coll/mi355x serves (NULL otherwise): for tools and tests */
 struct mi355x_comm *mca_coll_mi355x_engine_of(struct ompi_communicator_t *comm);
 

@@ -256,12 +256,20 @@ enum mi355x_knob {
     MI355X_KNOB_SELFTEST_REUSED = 43,   /* (read-only) flow verdicts this communicator took over from an earlier
                                            communicator of the same processes on the same GPUs (a dup / split):
                                            1 the device setup's (LL, pipelined), 2 also the service's */
-    MI355X_KNOB_NB_ORDER = 44           /* (per communicator, same value on every rank; env MI355X_NB_ORDER at
+    MI355X_KNOB_NB_ORDER = 44,          /* (per communicator, same value on every rank; env MI355X_NB_ORDER at
                                            creation; default 0) operand order of mi355x_iallreduce / _ireduce /
                                            _ireduce_scatter_block: 0 = coll/tuned's, as the blocking calls; 1 =
                                            coll/libnbc's, the component that serves them in the reference (its
                                            own selection, every step the 3-buff rule with the rank's own data
-                                           as in1).  Set only while no nonblocking call is pending. */
+                                           as in1); with 1 mi355x_iscan / _iexscan also run libnbc's form of
+                                           the rank chain.  Set only while no nonblocking call is pending. */
+    MI355X_KNOB_SCAN_PART_MIN_BYTES = 45 /* (per communicator, same value on every rank; env
+                                           MI355X_SCAN_PART_MIN_BYTES at creation; default 0: in the one-GPU
+                                           rehearsal the chain is ahead below 64 MiB per rank) scan /
+                                           exscan calls of at least this many bytes per rank, blocking or
+                                           nonblocking, take the partitioned flow (see mi355x_scan); 0 = never.
+                                           The results do not depend on it.  Set only while no nonblocking call
+                                           is pending. */
 };
 /* cross-device flows (MI355X_KNOB_FLOWS) */
 enum mi355x_flow {
@@ -331,7 +339,14 @@ int mi355x_bcast(mi355x_comm_t *comm, void *buf, size_t bytes, int root, void *s
  *   allgatherv  coll_tuned_allgatherv.c
  *   alltoall(v) coll_tuned_alltoall.c / coll_tuned_alltoallv.c
  *   scan, exscan  coll_basic_scan.c:40-120 / coll_basic_exscan.c:40-110 operand order, bit-exact:
- *               rank r = ((x0 op x1) op ...) op x_r (exscan: up to x_{r-1}; rank 0 untouched). */
+ *               rank r = ((x0 op x1) op ...) op x_r (exscan: up to x_{r-1}; rank 0 untouched).
+ *               Two flows, the same bits: the chain (last_algorithm 1), where rank r folds the r + 1
+ *               inputs by itself, and from MI355X_KNOB_SCAN_PART_MIN_BYTES per rank up the partitioned
+ *               flow (last_algorithm 2): rank q owns ring block q, evaluates that block of EVERY rank's
+ *               prefix in one pass over the n inputs (its own into rbuf, the others into its scratch),
+ *               and after a meeting point every rank pulls its other blocks from their owners.  The
+ *               chain serves communicators of one rank, slots without a fold kernel and buffers that
+ *               cannot be mapped. */
 int mi355x_gather(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes, int root, void *stream);
 int mi355x_gatherv(mi355x_comm_t *comm, const void *sbuf, size_t sbytes, void *rbuf, const size_t *rcounts,
                    const size_t *displs, int root, void *stream);
@@ -345,9 +360,14 @@ int mi355x_alltoallv(mi355x_comm_t *comm, const void *sbuf, const size_t *scount
                      void *rbuf, const size_t *rcounts, const size_t *rdispls, void *stream);
 int mi355x_scan(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t count, int type, int op, void *stream);
 int mi355x_exscan(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t count, int type, int op, void *stream);
+/* The partitioned scan flow's layout (host only, no GPU needed): owner q's block of a count-element
+ * vector over n ranks is elements [*src_off, *src_off + *len); rank r's prefix of that block sits at
+ * element *slot_off of q's scratch (n - 1 slots of *len elements; SIZE_MAX for r == q, whose prefix
+ * goes straight into its rbuf). */
+int mi355x_scan_part_plan(size_t count, int n, int q, int r, size_t *src_off, size_t *len, size_t *slot_off);
 
 /* Nonblocking collectives (MPI_Iallreduce, MPI_Ireduce, MPI_Ireduce_scatter_block, MPI_Iallgather,
- * MPI_Ibcast; the coll framework's nonblocking slots, coll.h:241-356, served in the reference by
+ * MPI_Ibcast, MPI_Iscan, MPI_Iexscan; the coll framework's nonblocking slots, coll.h:241-356, served in the reference by
  * coll/libnbc: nbc_iallreduce.c etc.).  Each call is queued behind the caller's prior work on
  * `stream` and run, in posting order, by the communicator's progress thread.  Under
  * MI355X_KNOB_NB_ORDER = 0 (the default) results are identical to the blocking call's, i.e.
@@ -356,7 +376,11 @@ int mi355x_exscan(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t coun
  * binomial or chain (nbc_ireduce.c:74-88), binomial + scatter (coll_libnbc_ireduce_scatter_block.c),
  * every step ompi_3buff_op_reduce; mi355x_comm_last_algorithm then reports 101 (binomial), 102
  * (ring) or 103 (chain), and a binomial tree over more than 16 ranks makes the posting call return
- * MI355X_ERR_UNSUPPORTED.  The other nonblocking calls do not depend on the knob.  A blocking
+ * MI355X_ERR_UNSUPPORTED.  iscan and iexscan then run libnbc's form of the rank chain
+ * (nbc_iscan.c:89-105, nbc_iexscan.c:94-135): the same shape as coll/basic's, every step the 3-buff
+ * rule with the rank's own data as in1 and the received partial as in2, so only MAXLOC / MINLOC
+ * change bits; iexscan leaves rank 0's rbuf untouched either way.  The other nonblocking calls do
+ * not depend on the knob.  A blocking
  * collective on the same communicator first waits for every posted one.  Requests: test (non-blocking; *done = 1 once finished, then returns the
  * collective's status), wait (blocks; returns the status), free (only once finished). */
 typedef struct mi355x_request mi355x_request_t;
@@ -371,6 +395,8 @@ int mi355x_iallgather(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t 
 int mi355x_ibcast(mi355x_comm_t *comm, void *buf, size_t bytes, int root, void *stream, mi355x_request_t **req);
 int mi355x_iscan(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t count, int type, int op, void *stream,
                  mi355x_request_t **req);
+int mi355x_iexscan(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t count, int type, int op, void *stream,
+                   mi355x_request_t **req);
 int mi355x_ialltoall(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes, void *stream,
                      mi355x_request_t **req);
 int mi355x_request_test(mi355x_request_t *req, int *done);

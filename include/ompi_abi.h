@@ -528,6 +528,8 @@ typedef int (*mca_coll_base_module_iallgather_fn_t)(void *sbuf, int scount, stru
 typedef int (*mca_coll_base_module_iallreduce_fn_t)(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype,
                                                     struct ompi_op_t *op, struct ompi_communicator_t *comm,
                                                     ompi_request_t **request, mca_coll_base_module_t *module);
+typedef mca_coll_base_module_iallreduce_fn_t mca_coll_base_module_iscan_fn_t;    /* coll.h:340-356 */
+typedef mca_coll_base_module_iallreduce_fn_t mca_coll_base_module_iexscan_fn_t;
 typedef int (*mca_coll_base_module_ibcast_fn_t)(void *buff, int count, struct ompi_datatype_t *datatype, int root,
                                                 struct ompi_communicator_t *comm, ompi_request_t **request,
                                                 mca_coll_base_module_t *module);
@@ -570,11 +572,13 @@ struct mca_coll_base_module_2_0_0_t {
     mca_coll_base_module_iallreduce_fn_t coll_iallreduce;
     mca_coll_base_any_fn_t coll_ialltoall, coll_ialltoallv, coll_ialltoallw, coll_ibarrier;
     mca_coll_base_module_ibcast_fn_t coll_ibcast;
-    mca_coll_base_any_fn_t coll_iexscan, coll_igather, coll_igatherv;
+    mca_coll_base_module_iexscan_fn_t coll_iexscan;
+    mca_coll_base_any_fn_t coll_igather, coll_igatherv;
     mca_coll_base_module_ireduce_fn_t coll_ireduce;
     mca_coll_base_any_fn_t coll_ireduce_scatter;
     mca_coll_base_module_ireduce_scatter_block_fn_t coll_ireduce_scatter_block;
-    mca_coll_base_any_fn_t coll_iscan, coll_iscatter, coll_iscatterv;
+    mca_coll_base_module_iscan_fn_t coll_iscan;
+    mca_coll_base_any_fn_t coll_iscatter, coll_iscatterv;
     mca_coll_base_any_fn_t coll_neighbor[10];
     mca_coll_base_module_ft_event_fn_t ft_event;
 };
@@ -624,13 +628,17 @@ typedef struct mca_coll_base_comm_coll_t {
     struct { mca_coll_base_any_fn_t fn; mca_coll_base_module_t *module; } coll_ia2a[4];  /* ialltoall(v,w), ibarrier */
     mca_coll_base_module_ibcast_fn_t coll_ibcast;
     mca_coll_base_module_t *coll_ibcast_module;
-    struct { mca_coll_base_any_fn_t fn; mca_coll_base_module_t *module; } coll_iegg[3];  /* iexscan, igather(v) */
+    mca_coll_base_module_iexscan_fn_t coll_iexscan;
+    mca_coll_base_module_t *coll_iexscan_module;
+    struct { mca_coll_base_any_fn_t fn; mca_coll_base_module_t *module; } coll_igg[2];  /* igather(v) */
     mca_coll_base_module_ireduce_fn_t coll_ireduce;
     mca_coll_base_module_t *coll_ireduce_module;
     struct { mca_coll_base_any_fn_t fn; mca_coll_base_module_t *module; } coll_ireduce_scatter_pair;
     mca_coll_base_module_ireduce_scatter_block_fn_t coll_ireduce_scatter_block;
     mca_coll_base_module_t *coll_ireduce_scatter_block_module;
-    struct { mca_coll_base_any_fn_t fn; mca_coll_base_module_t *module; } coll_isss[3];  /* iscan, iscatter(v) */
+    mca_coll_base_module_iscan_fn_t coll_iscan;
+    mca_coll_base_module_t *coll_iscan_module;
+    struct { mca_coll_base_any_fn_t fn; mca_coll_base_module_t *module; } coll_iss[2];  /* iscatter(v) */
     struct { mca_coll_base_any_fn_t fn; mca_coll_base_module_t *module; } coll_neighbor[10];
 } mca_coll_base_comm_coll_t;
 

@@ -174,6 +174,8 @@ def _declare(lib: ctypes.CDLL) -> None:
         "mi355x_scan": (i, [vp, vp, vp, sz, i, i, vp]),
         "mi355x_exscan": (i, [vp, vp, vp, sz, i, i, vp]),
         "mi355x_iscan": (i, [vp, vp, vp, sz, i, i, vp, c.POINTER(vp)]),
+        "mi355x_iexscan": (i, [vp, vp, vp, sz, i, i, vp, c.POINTER(vp)]),
+        "mi355x_scan_part_plan": (i, [sz, i, i, i, c.POINTER(sz), c.POINTER(sz), c.POINTER(sz)]),
         "mi355x_ialltoall": (i, [vp, vp, vp, sz, vp, c.POINTER(vp)]),
         "mi355x_isend": (i, [vp, vp, sz, vp, i, i, vp, c.POINTER(vp)]),
         "mi355x_irecv": (i, [vp, vp, sz, vp, i, i, vp, c.POINTER(vp)]),
@@ -257,6 +259,15 @@ def get_tune() -> tuple[int, int, int]:
 
 
 # ---------------------------------------------------------------- coll/mi355x engine
+def scan_part_plan(count: int, n: int, q: int, r: int) -> tuple[int, int, int | None]:
+    """the partitioned scan flow's layout (host only): owner q's block (first element, length) and the
+    element of q's scratch where rank r's prefix of that block sits (None for r == q: it goes to rbuf)"""
+    a, b, c_ = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    check(rt().mi355x_scan_part_plan(count, n, q, r, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c_)),
+          "mi355x_scan_part_plan")
+    return a.value, b.value, None if r == q else c_.value
+
+
 KNOB = {"ALLREDUCE_ALG": 1, "REDUCE_ALG": 2, "REDUCE_SCATTER_ALG": 3, "BLOCKS_PER_CU": 4, "TIMEOUT_S": 5,
         "PUSH": 6, "IPC_MAX_BYTES": 7, "STAGE_BYTES": 8,
         "LL_MAX_BYTES": 9, "REDUCE_CHAIN_FANOUT": 10, "TIME_PHASES": 11,
@@ -267,7 +278,8 @@ KNOB = {"ALLREDUCE_ALG": 1, "REDUCE_ALG": 2, "REDUCE_SCATTER_ALG": 3, "BLOCKS_PE
         "RCACHE_EVICTIONS": 28, "FLOWS": 29, "FLOWS_FAILED": 30, "CREATE_US": 31, "SELFTEST_US": 32,
         "SVC_OWNER": 33, "SVC_CLAIMS": 34, "SVC_IDLE_US": 35,
         "SVC_SHRINK_US": 36, "SVC_REGROWS": 37, "DEV_SETUP": 38, "SETUP_US": 39, "SELFTEST": 40,
-        "PIPE_CALLS": 41, "EXPORT_MISMATCHES": 42, "SELFTEST_REUSED": 43, "NB_ORDER": 44}
+        "PIPE_CALLS": 41, "EXPORT_MISMATCHES": 42, "SELFTEST_REUSED": 43, "NB_ORDER": 44,
+        "SCAN_PART_MIN_BYTES": 45}
 # coll/libnbc's algorithms (mi355x_comm_last_algorithm under NB_ORDER = 1, mi355x_nbc_decision)
 NBC_ALG = {"BINOMIAL": 101, "RING": 102, "CHAIN": 103}
 FLOW = {"SVC_LL": 1, "SVC_PULL": 2, "SVC_COPY": 4, "SVC_RS": 8, "PIPE": 16}
@@ -423,6 +435,9 @@ class Comm:
 
     def iscan(self, sbuf, rbuf, count, ty, op, stream=None) -> Request:
         return self._post("mi355x_iscan", sbuf, rbuf, count, ty, op, stream)
+
+    def iexscan(self, sbuf, rbuf, count, ty, op, stream=None) -> Request:
+        return self._post("mi355x_iexscan", sbuf, rbuf, count, ty, op, stream)
 
     def ialltoall(self, sbuf, rbuf, nbytes, stream=None) -> Request:
         return self._post("mi355x_ialltoall", sbuf, rbuf, nbytes, stream)

@@ -429,6 +429,8 @@ void mini_comm_install(ompi_communicator_t *c, mca_coll_base_module_t *m)
     INST(ibcast)
     INST(ireduce)
     INST(ireduce_scatter_block)
+    INST(iscan)
+    INST(iexscan)
     INST(gather)
     INST(gatherv)
     INST(scatter)
@@ -488,6 +490,8 @@ void mini_comm_destroy(ompi_communicator_t *c)
     REL(ibcast)
     REL(ireduce)
     REL(ireduce_scatter_block)
+    REL(iscan)
+    REL(iexscan)
     REL(gather)
     REL(gatherv)
     REL(scatter)
@@ -845,6 +849,16 @@ int mini_exscan(ompi_communicator_t *c, void *s, void *r, int n, ompi_datatype_t
     return c->c_coll.coll_exscan(s, r, n, d, op, c, c->c_coll.coll_exscan_module);
 }
 
+int mini_iscan(ompi_communicator_t *c, void *s, void *r, int n, ompi_datatype_t *d, ompi_op_t *op, ompi_request_t **req)
+{
+    return c->c_coll.coll_iscan(s, r, n, d, op, c, req, c->c_coll.coll_iscan_module);
+}
+int mini_iexscan(ompi_communicator_t *c, void *s, void *r, int n, ompi_datatype_t *d, ompi_op_t *op,
+                 ompi_request_t **req)
+{
+    return c->c_coll.coll_iexscan(s, r, n, d, op, c, req, c->c_coll.coll_iexscan_module);
+}
+
 void *mini_comm_fn(ompi_communicator_t *c, int which)
 {
     switch (which) {
@@ -868,6 +882,8 @@ void *mini_comm_fn(ompi_communicator_t *c, int which)
     case 17: return (void *)c->c_coll.coll_alltoallv;
     case 18: return (void *)c->c_coll.coll_scan;
     case 19: return (void *)c->c_coll.coll_exscan;
+    case 20: return (void *)c->c_coll.coll_iscan;
+    case 21: return (void *)c->c_coll.coll_iexscan;
     default: return NULL;
     }
 }
@@ -1067,6 +1083,10 @@ static int st_iallreduce(void *s, void *r, int n, struct ompi_datatype_t *d, str
                          struct ompi_communicator_t *c, ompi_request_t **req, mca_coll_base_module_t *m)
 { if (guard("st_iallreduce", 2, s, r)) return MINI_ERR_DEVICE_BUFFER; (void)s; (void)r; (void)n; (void)d; (void)o; (void)c; (void)m; *req = &ompi_request_null.request; stub_calls[6]++; return stub_marker; }
 
+static int st_iscan(void *s, void *r, int n, struct ompi_datatype_t *d, struct ompi_op_t *o,
+                    struct ompi_communicator_t *c, ompi_request_t **req, mca_coll_base_module_t *m)
+{ if (guard("st_iscan", 2, s, r)) return MINI_ERR_DEVICE_BUFFER; (void)s; (void)r; (void)n; (void)d; (void)o; (void)c; (void)m; *req = &ompi_request_null.request; stub_calls[14]++; return stub_marker; }
+
 static int st_gather(void *s, int sc, struct ompi_datatype_t *sd, void *r, int rc, struct ompi_datatype_t *rd,
                      int root, struct ompi_communicator_t *c, mca_coll_base_module_t *m)
 { if (guard("st_gather", 2, s, r)) return MINI_ERR_DEVICE_BUFFER; (void)s; (void)sc; (void)sd; (void)r; (void)rc; (void)rd; (void)root; (void)c; (void)m; stub_calls[7]++; return stub_marker; }
@@ -1099,6 +1119,8 @@ mca_coll_base_module_t *mini_stub_module(void)
     m->coll_bcast = st_bcast;
     m->coll_reduce = st_reduce;
     m->coll_iallreduce = st_iallreduce;
+    m->coll_iscan = st_iscan;
+    m->coll_iexscan = st_iscan;
     m->coll_gather = st_gather;
     m->coll_scatter = st_gather;
     m->coll_alltoall = st_alltoall;
@@ -1124,7 +1146,7 @@ int mini_stub_marker(void) { return stub_marker; }
  * 63-104).  Types: any with true_lb == 0 (instances extent apart, true_ub bytes each).  Nonblocking
  * forms are queued and run in order from an opal_progress callback, so their requests complete
  * only under MPI_Wait / MPI_Test, as libnbc's do.  Every buffer passes the device guard. */
-static int host_calls[16];
+static int host_calls[20];
 
 static void host_op_reduce(ompi_op_t *op, void *in, void *inout, int count, ompi_datatype_t *dt)
 {
@@ -1443,7 +1465,7 @@ static int h_alltoall(void *s, int sc, struct ompi_datatype_t *sd, void *r, int 
 /* ---- nonblocking: queued, run in posting order from the progress callback */
 typedef struct mini_hreq {
     ompi_request_t super;
-    int kind;  /* 0 allreduce, 1 reduce, 2 rsb, 3 allgather, 4 bcast */
+    int kind;  /* 0 allreduce, 1 reduce, 2 rsb, 3 allgather, 4 bcast, 5 scan, 6 exscan */
     void *s, *r;
     int n, n2, root;
     struct ompi_datatype_t *d, *d2;
@@ -1480,6 +1502,8 @@ static int hq_progress(void)
         case 1: rc = h_reduce(q->s, q->r, q->n, q->d, q->o, q->root, q->c, NULL); break;
         case 2: rc = h_rsb(q->s, q->r, q->n, q->d, q->o, q->c, NULL); break;
         case 3: rc = h_allgather(q->s, q->n, q->d, q->r, q->n2, q->d2, q->c, NULL); break;
+        case 5: rc = h_scan(q->s, q->r, q->n, q->d, q->o, q->c, NULL); break;
+        case 6: rc = h_exscan(q->s, q->r, q->n, q->d, q->o, q->c, NULL); break;
         default: rc = h_bcast(q->r, q->n, q->d, q->root, q->c, NULL); break;
         }
         q->super.req_status.MPI_ERROR = rc;
@@ -1539,6 +1563,22 @@ static int h_irsb(void *s, void *r, int n, struct ompi_datatype_t *d, struct omp
     if (guard("ireduce_scatter_block", 2, s, r)) return MINI_ERR_DEVICE_BUFFER;
     return hq_post((mini_hreq_t){.kind = 2, .s = s, .r = r, .n = n, .d = d, .o = o, .c = c}, req);
 }
+static int h_iscan(void *s, void *r, int n, struct ompi_datatype_t *d, struct ompi_op_t *o,
+                   struct ompi_communicator_t *c, ompi_request_t **req, mca_coll_base_module_t *m)
+{
+    (void)m;
+    host_calls[15]++;
+    if (guard("iscan", 2, s, r)) return MINI_ERR_DEVICE_BUFFER;
+    return hq_post((mini_hreq_t){.kind = 5, .s = s, .r = r, .n = n, .d = d, .o = o, .c = c}, req);
+}
+static int h_iexscan(void *s, void *r, int n, struct ompi_datatype_t *d, struct ompi_op_t *o,
+                     struct ompi_communicator_t *c, ompi_request_t **req, mca_coll_base_module_t *m)
+{
+    (void)m;
+    host_calls[16]++;
+    if (guard("iexscan", 2, s, r)) return MINI_ERR_DEVICE_BUFFER;
+    return hq_post((mini_hreq_t){.kind = 6, .s = s, .r = r, .n = n, .d = d, .o = o, .c = c}, req);
+}
 static int h_iallgather(void *s, int sc, struct ompi_datatype_t *sd, void *r, int rc, struct ompi_datatype_t *rd,
                         struct ompi_communicator_t *c, ompi_request_t **req, mca_coll_base_module_t *m)
 {
@@ -1575,10 +1615,12 @@ mca_coll_base_module_t *mini_host_module(void)
     m->coll_ireduce = h_ireduce;
     m->coll_ireduce_scatter_block = h_irsb;
     m->coll_iallgather = h_iallgather;
+    m->coll_iscan = h_iscan;
+    m->coll_iexscan = h_iexscan;
     m->coll_ibcast = h_ibcast;
     return m;
 }
-int mini_host_calls(int which) { return (which >= 0 && which < 16) ? host_calls[which] : -1; }
+int mini_host_calls(int which) { return (which >= 0 && which < 20) ? host_calls[which] : -1; }
 
 /* MPI_Op_create (ompi_op_create_user, op.c:351-400): not intrinsic, commutative or not, the C
  * function in o_func.c_fn; its f2c index lies past the predefined ops */

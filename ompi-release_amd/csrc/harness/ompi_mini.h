@@ -38,7 +38,10 @@ int mini_reduce_scatter_block(ompi_communicator_t *c, void *s, void *r, int n, o
 int mini_reduce_scatter(ompi_communicator_t *c, void *s, void *r, int *rc, ompi_datatype_t *d, ompi_op_t *op);
 int mini_allgather(ompi_communicator_t *c, void *s, int sc, ompi_datatype_t *sd, void *r, int rc, ompi_datatype_t *rd);
 int mini_bcast(ompi_communicator_t *c, void *b, int n, ompi_datatype_t *d, int root);
-void *mini_comm_fn(ompi_communicator_t *c, int which);
+int mini_iscan(ompi_communicator_t *c, void *s, void *r, int n, ompi_datatype_t *d, ompi_op_t *op, ompi_request_t **req);
+int mini_iexscan(ompi_communicator_t *c, void *s, void *r, int n, ompi_datatype_t *d, ompi_op_t *op,
+                 ompi_request_t **req);
+void *mini_comm_fn(ompi_communicator_t *c, int which);  /* 20 / 21: the iscan / iexscan slots */
 mca_coll_base_module_t *mini_stub_module(void);
 int mini_stub_calls(int which);
 int mini_stub_marker(void);

@@ -57,6 +57,10 @@ typedef struct mca_coll_mi355x_module_t {
     /* nonblocking slots: the previous owner (normally coll/libnbc) may be absent */
     mca_coll_base_module_iallreduce_fn_t prev_iallreduce;
     mca_coll_base_module_t *prev_iallreduce_module;
+    mca_coll_base_module_iscan_fn_t prev_iscan;
+    mca_coll_base_module_t *prev_iscan_module;
+    mca_coll_base_module_iexscan_fn_t prev_iexscan;
+    mca_coll_base_module_t *prev_iexscan_module;
     mca_coll_base_module_ireduce_fn_t prev_ireduce;
     mca_coll_base_module_t *prev_ireduce_module;
     mca_coll_base_module_ireduce_scatter_block_fn_t prev_ireduce_scatter_block;
@@ -105,6 +109,8 @@ static void module_destruct(opal_object_t *o)
     release_prev(m->prev_scan_module);
     release_prev(m->prev_exscan_module);
     release_prev(m->prev_iallreduce_module);
+    release_prev(m->prev_iscan_module);
+    release_prev(m->prev_iexscan_module);
     release_prev(m->prev_ireduce_module);
     release_prev(m->prev_ireduce_scatter_block_module);
     release_prev(m->prev_iallgather_module);
@@ -334,6 +340,7 @@ int mca_coll_mi355x_svc_idle_us = 1000;
 int mca_coll_mi355x_svc_shrink_us = 100;
 int mca_coll_mi355x_selftest = 1;
 int mca_coll_mi355x_nb_order = 0;
+unsigned long long mca_coll_mi355x_scan_part_min = 0;  /* measured: BASELINE.md, "Partitioned scan" */
 int mca_coll_mi355x_timeout_s = 0;  /* 0: the engine's own (MI355X_TIMEOUT_S, else one day) */
 
 /* 1: the call runs in the engine (a rank with host buffers joins on device copies); 0: it runs in
@@ -1569,6 +1576,63 @@ int mca_coll_mi355x_ireduce_scatter_block(void *sbuf, void *rbuf, int rcount, st
     NB_STAGED(ireduce_scatter_block, in, inplace ? in : out, inplace, out, dtype, sbuf, rbuf, rcount, dtype, op, comm);
 }
 
+/* MPI_Iscan / MPI_Iexscan: in the reference coll/libnbc's, whose schedule copies through a host
+ * tmpbuf and reduces with one host and one device operand (nbc_iscan.c:64-96, nbc_iexscan.c:69-126)
+ * -- not usable on device buffers.  Shaped like iallreduce above; an exscan's rbuf is also filled
+ * in (rank 0's is left as it was, so a staged or joined copy must start from its contents). */
+static int iscan_common(int exclusive, void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype,
+                        struct ompi_op_t *op, struct ompi_communicator_t *comm, ompi_request_t **request,
+                        mca_coll_base_module_t *module)
+{
+    mca_coll_mi355x_module_t *m = MOD(module);
+    const int inplace = (sbuf == MPI_IN_PLACE);
+    const int t = reducible_type(dtype);
+#define ISCAN_STAGED()                                                                                      \
+    do {                                                                                                    \
+        const size_t span = dt_span(dtype, (size_t)count);                                                  \
+        if (exclusive) NB_STAGED(iexscan, span, span, 1, span, dtype, sbuf, rbuf, count, dtype, op, comm);  \
+        NB_STAGED(iscan, span, span, inplace, span, dtype, sbuf, rbuf, count, dtype, op, comm);             \
+    } while (0)
+    if (count < 0) {
+        if (exclusive) NB_FALLBACK(iexscan, sbuf, rbuf, count, dtype, op, comm, request);
+        NB_FALLBACK(iscan, sbuf, rbuf, count, dtype, op, comm, request);
+    }
+    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
+    if (!engine_op(op, t) || (!dev && !m->mixed)) ISCAN_STAGED();
+    mi355x_request_t *eng = NULL;
+    if (!dev) {  /* host buffers: join the engine on device copies (nb_host_join) */
+        const size_t bytes = (size_t)count * mi355x_type_size(t);
+        struct nb_stage st;
+        void *sd, *rd;
+        int rc = nb_host_join(m, sbuf, rbuf, inplace, bytes, bytes, 1, &sd, &rd, &st);
+        if (rc == MI355X_SUCCESS && exclusive && !inplace && st.uhost && bytes) rc = mi355x_memcpy(rd, rbuf, bytes);
+        if (rc == MI355X_SUCCESS)
+            rc = (exclusive ? mi355x_iexscan : mi355x_iscan)(m->engine, sd, rd, (size_t)count, t, op->o_f_to_c_index, NULL,
+                                                             &eng);
+        if (rc == MI355X_SUCCESS) return nb_start_full(eng, comm, request, 0, &st);
+        nb_stage_release(&st);
+        if (!NB_UNFIT(rc)) return map_rc(rc);
+    } else {
+        int rc = (exclusive ? mi355x_iexscan : mi355x_iscan)(m->engine, inplace ? NULL : sbuf, rbuf, (size_t)count, t,
+                                                             op->o_f_to_c_index, NULL, &eng);
+        if (!NB_UNFIT(rc)) return rc ? map_rc(rc) : nb_start(eng, comm, request);
+    }
+    ISCAN_STAGED();
+#undef ISCAN_STAGED
+}
+
+int mca_coll_mi355x_iscan(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
+                          struct ompi_communicator_t *comm, ompi_request_t **request, mca_coll_base_module_t *module)
+{
+    return iscan_common(0, sbuf, rbuf, count, dtype, op, comm, request, module);
+}
+
+int mca_coll_mi355x_iexscan(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
+                            struct ompi_communicator_t *comm, ompi_request_t **request, mca_coll_base_module_t *module)
+{
+    return iscan_common(1, sbuf, rbuf, count, dtype, op, comm, request, module);
+}
+
 /* the (count, dt) side of a staged nonblocking move: pack it into `p` now (local work), or set up
  * the completion-time unpack into `st` (the request then owns a private layout of dt) */
 static int nb_stage_side(int pack, void *buf, size_t count, const struct ompi_datatype_t *dt, void *p, size_t bytes,
@@ -2158,6 +2222,7 @@ static int apply_engine_params(mca_coll_mi355x_module_t *m, struct ompi_communic
 #define KNOB(K, V, NAME) if (rc == OMPI_SUCCESS) rc = set_knob(m, MI355X_KNOB_##K, (long)(V), NAME)
     KNOB(SELFTEST, mca_coll_mi355x_selftest != 0, "selftest");
     KNOB(NB_ORDER, mca_coll_mi355x_nb_order != 0, "nb_order");
+    KNOB(SCAN_PART_MIN_BYTES, mca_coll_mi355x_scan_part_min, "scan_part_min_bytes");
     KNOB(PIPE, mca_coll_mi355x_pipe_min_ranks > 0 && n >= mca_coll_mi355x_pipe_min_ranks, "pipe_min_ranks");
     KNOB(PIPE_CHUNK_KIB, mca_coll_mi355x_pipe_chunk_kib, "pipe_chunk_kib");
     KNOB(PIPE_WG_PER_CU, mca_coll_mi355x_pipe_wg_per_cu, "pipe_wg_per_cu");
@@ -2205,6 +2270,8 @@ static int module_enable(mca_coll_base_module_t *module, struct ompi_communicato
     SNAP_OPT(ireduce_scatter_block);
     SNAP_OPT(iallgather);
     SNAP_OPT(ibcast);
+    SNAP_OPT(iscan);
+    SNAP_OPT(iexscan);
     /* Node-unique rendezvous key, picked by rank 0 and broadcast with the lower-priority bcast
      * just snapshotted (the communicator is p2p-capable during enable, coll.h:125-127).  Neither
      * the job id nor the context id would do: MPI_Comm_split allocates ONE cid for every color
@@ -2319,6 +2386,10 @@ static int component_register(void)
                  "0 = coll/tuned's, as the blocking calls; 1 = coll/libnbc's, the component that serves them otherwise "
                  "(a libnbc tree the device cannot hold goes to that component)", OPAL_INFO_LVL_6,
                  &mca_coll_mi355x_nb_order);
+    register_ull("scan_part_min_bytes", "Per-rank message bytes from which MPI_Scan / MPI_Exscan and their nonblocking "
+                 "forms take the engine's partitioned flow (each rank evaluates one block of every rank's prefix, "
+                 "then the blocks are pulled) instead of the chain; 0 = never; the results do not depend on it",
+                 OPAL_INFO_LVL_6, &mca_coll_mi355x_scan_part_min);
     register_int("timeout_s", "Bound of every wait of the engine, seconds (0 = the engine's own: MI355X_TIMEOUT_S, "
                  "else one day -- MPI's waits are unbounded; a rank whose process is gone is noticed without it)",
                  OPAL_INFO_LVL_9, &mca_coll_mi355x_timeout_s);
@@ -2372,6 +2443,8 @@ static mca_coll_base_module_t *component_comm_query(struct ompi_communicator_t *
     m->super.coll_scan = mca_coll_mi355x_scan;
     m->super.coll_exscan = mca_coll_mi355x_exscan;
     m->super.coll_iallreduce = mca_coll_mi355x_iallreduce;
+    m->super.coll_iscan = mca_coll_mi355x_iscan;
+    m->super.coll_iexscan = mca_coll_mi355x_iexscan;
     m->super.coll_ireduce = mca_coll_mi355x_ireduce;
     m->super.coll_ireduce_scatter_block = mca_coll_mi355x_ireduce_scatter_block;
     m->super.coll_iallgather = mca_coll_mi355x_iallgather;

@@ -184,6 +184,7 @@ int mi355x_comm_create(const char *key, int rank, int size, int device, mi355x_c
     c->pipe_on = env_double("MI355X_PIPE", size >= 4 ? 1.0 : 0.0) != 0.0;
     c->one_phase_max = (size_t)std::max(0.0, env_double("MI355X_ONE_PHASE_MAX_BYTES", (double)c->one_phase_max));
     c->nb_order = env_double("MI355X_NB_ORDER", 0.0) != 0.0 ? 1 : 0;
+    c->scan_part_min = (size_t)std::max(0.0, env_double("MI355X_SCAN_PART_MIN_BYTES", (double)kScanPartMinDefault));
     c->lat_on = env_double("MI355X_LAT_PROFILE", 0.0) != 0.0;
     c->rcache_max_maps = (size_t)std::max(0.0, env_double("MI355X_RCACHE_MAX_MAPS", 0.0));
     c->rcache_limit = (size_t)std::max(0.0, env_double("MI355X_RCACHE_SIZE_LIMIT", 0.0));
@@ -218,6 +219,7 @@ int mi355x_comm_create_loopback(int size, int device, mi355x_comm_t **comms)
         c->loop = shared;
         c->timeout_s = env_double("MI355X_TIMEOUT_S", kDefaultTimeoutS);
         c->nb_order = env_double("MI355X_NB_ORDER", 0.0) != 0.0 ? 1 : 0;
+        c->scan_part_min = (size_t)std::max(0.0, env_double("MI355X_SCAN_PART_MIN_BYTES", (double)kScanPartMinDefault));
         shared->refs++;
         comms[r] = c;
     }
@@ -480,6 +482,7 @@ int mi355x_comm_get(const mi355x_comm_t *c, int knob, long *value)
     }
     case MI355X_KNOB_RCACHE_EVICTIONS: *value = (long)c->rcache_evictions; break;
     case MI355X_KNOB_NB_ORDER: *value = c->nb_order; break;
+    case MI355X_KNOB_SCAN_PART_MIN_BYTES: *value = (long)c->scan_part_min; break;
     default: return set_error(MI355X_ERR_ARG, "unknown knob %d", knob);
     }
     return MI355X_SUCCESS;
@@ -608,6 +611,14 @@ int mi355x_comm_set(mi355x_comm_t *c, int knob, long value)
         std::lock_guard<std::mutex> g(c->q_mtx);
         if (c->pending) return set_error(MI355X_ERR_ARG, "nb_order may change only while no nonblocking call is pending");
         c->nb_order = (int)value;
+        break;
+    }
+    case MI355X_KNOB_SCAN_PART_MIN_BYTES: {
+        if (value < 0) return set_error(MI355X_ERR_ARG, "scan_part_min_bytes out of range");
+        // (the ranks must agree on a call's flow: as nb_order, not while a posted call may have read it)
+        std::lock_guard<std::mutex> g(c->q_mtx);
+        if (c->pending) return set_error(MI355X_ERR_ARG, "scan_part_min_bytes may change only while no nonblocking call is pending");
+        c->scan_part_min = (size_t)value;
         break;
     }
     case MI355X_KNOB_STAGE_BYTES:

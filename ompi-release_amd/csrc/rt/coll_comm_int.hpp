@@ -157,7 +157,8 @@ int gfold_reduce_scatter_block(mi355x_comm *c, const void *in, void *rbuf, size_
                                hipStream_t s, bool nbc = false);
 int gfold_reduce_scatter(mi355x_comm *c, const void *in, void *rbuf, const size_t *disp, int type, int op,
                          hipStream_t s);
-int gfold_scan(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, int last, hipStream_t s);
+int gfold_scan(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, int last, hipStream_t s,
+               bool three = false);
 hipStream_t setup_stream(mi355x_comm *c);
 int ensure_pipe(mi355x_comm *c);
 int pipe_allreduce(mi355x_comm *c, int op, int type, const Program &pr,

@@ -271,9 +271,11 @@ int gfold_reduce_scatter(mi355x_comm *c, const void *in, void *rbuf, const size_
     return gather_fold(c, in, count, type, op, std::vector<GfSeg>(1, sg), s);
 }
 
-int gfold_scan(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, int last, hipStream_t s)
+int gfold_scan(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, int last, hipStream_t s,
+               bool three)
 {
     // coll/basic's chain: p = r[0]; p = op2(out = r[k], in = p) for k = 1..last
+    // (three: coll/libnbc's, p = op3(in1 = r[k], in2 = p))
     std::vector<GfSeg> segs;
     if (last >= 0) {
         GfSeg sg;
@@ -281,6 +283,7 @@ int gfold_scan(mi355x_comm *c, const void *in, void *rbuf, size_t count, int typ
         sg.pr.nr = last + 1;
         for (int k = 0; k <= last; ++k) sg.pr.order.push_back(k);
         sg.pr.role_mask = 0;
+        sg.pr.three = three;
         sg.e0 = 0;
         sg.ne = count;
         sg.dst = static_cast<char *>(rbuf);

@@ -27,6 +27,21 @@ struct FoldArgs {
     int three;
 };
 
+// k_scan_part: every prefix of the rank chain in one pass over the launch's elements --
+// acc = x_0; acc = op2(out = x_k, in = acc) for k = 1.. (three: op3(in1 = x_k, in2 = acc)), the
+// accumulator after step k stored to dst[k] (inclusive) or dst[k + 1] (exclusive: x_{nr-1} is
+// never loaded and dst[0] never written).  dst[r] may alias src[r]: a lane has loaded x_r[i]
+// before it stores anything to dst[r] at i.
+struct ScanArgs {
+    const void *src[kMaxRanks];  // rank inputs, already offset to this launch's first element
+    void *dst[kMaxRanks];        // where each rank's prefix goes, same offset
+    int nr;                      // ranks
+    int exclusive;
+    size_t n;                    // elements
+    size_t head, nvec;           // filled by the launcher
+    int three;
+};
+
 struct TreeStep {
     int8_t dst, out, in;         // R[dst] = op2(out = R[out], in = R[in])
 };
@@ -224,6 +239,7 @@ CollTune &coll_tune_default();  // the process defaults new communicators start 
 CollTune *coll_tune_use(CollTune *t);  // install t for this thread; returns the previous one
 
 int launch_fold_slot(int op, int type, const FoldArgs &a, hipStream_t s);
+int launch_scan_slot(int op, int type, const ScanArgs &a, hipStream_t s);
 int launch_ring_all_slot(int op, int type, const RingAllArgs &a, hipStream_t s);
 int launch_tree_slot(int op, int type, const TreeArgs &a, hipStream_t s);
 int launch_copy(CopyArgs a, hipStream_t s);

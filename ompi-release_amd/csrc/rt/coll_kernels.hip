@@ -14,6 +14,8 @@
 //             which keeps the left-fold order.
 //   k_tree  : a register program R[dst] = op2(out=R[o], in=R[i]) over <= 16 rank inputs --
 //             the recursive-doubling butterfly (:193-284), binomial / binary reduce trees.
+//   k_scan_part : every prefix of the rank chain (MPI_Scan / MPI_Exscan) in one pass: a running
+//             accumulator per element, one destination per rank, k_fold's load chunks.
 //   k_copy  : no arithmetic (allgather, bcast slices): one source, many destinations.
 // k_fold, k_tree and k_ring_all also have a 3-buff form (template parameter THREE: op3(in1, in2) in
 // place of op2(out, in)) for coll/libnbc's programs (Program::three, coll_nbc.cpp), and k_ring_all a
@@ -189,6 +191,105 @@ __global__ __launch_bounds__(256) void k_fold(FoldArgs a)
         const T r = fold_scalar<F, THREE>(a, i);
         for (int d = 0; d < a.nd; ++d) static_cast<T *>(a.dst[d])[i] = r;
     }
+}
+
+// ------------------------------------------------------------------ rank-chain prefixes, one pass
+// MPI_Scan / MPI_Exscan over the elements one rank owns: one running accumulator per element
+// yields every rank's prefix in the chain's own order (acc is `in` / `in2` at every step, as
+// coll/basic's ompi_op_reduce(op, partial, x_k) and libnbc's op(recvbuf, sendbuf, tmp)).  The
+// prefix after step k goes to dst[k + exclusive].  dst[r] may alias src[r] (MPI_IN_PLACE), so every
+// store to dst[r] comes, in program order, after the lane's load of x_r at the same position:
+// inclusive, x_k is part of the value stored; exclusive, x_{k+1} is in the chunk of loads already
+// issued, or -- when k closes a chunk -- the store is held back (`pend`) until the next chunk's
+// loads have been issued.  dst[nr-1] of the exclusive form aliases an input nobody reads.
+template <class F, bool THREE>
+__device__ __forceinline__ void scan_scalar(const ScanArgs &a, int nl, size_t i)
+{
+    using T = typename F::T;
+    T x = static_cast<const T *>(a.src[0])[i];
+    T acc = x;
+    for (int k = 0; k < nl; ++k) {
+        T nx = x;
+        if (k + 1 < nl) nx = static_cast<const T *>(a.src[k + 1])[i];  // before the store below
+        if (k) acc = rule<F, THREE>(x, acc);
+        static_cast<T *>(a.dst[k + a.exclusive])[i] = acc;
+        x = nx;
+    }
+}
+
+template <class F, int U, bool NT, bool THREE>
+__global__ __launch_bounds__(256) void k_scan_part(ScanArgs a)
+{
+    using T = typename F::T;
+    using V = CVec<T>;
+    constexpr int EPV = 16 / sizeof(T);
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t nthr = (size_t)gridDim.x * blockDim.x;
+    const int ex = a.exclusive ? 1 : 0;
+    const int nl = a.nr - ex;  // sources loaded
+    if (nl <= 0) return;
+
+    for (size_t i = tid; i < a.head; i += nthr) scan_scalar<F, THREE>(a, nl, i);
+
+    const size_t nvec = a.nvec;
+    const size_t hb = a.head * sizeof(T);
+    for (size_t base = tid; base < nvec; base += nthr * U) {
+        V acc[U];
+        int pend = -1;  // destination whose store waits for the next chunk's loads
+        for (int j0 = 0; j0 < nl; j0 += kFoldChunk) {
+            V x[kFoldChunk][U];
+#pragma unroll
+            for (int j = 0; j < kFoldChunk; ++j) {
+                if (j0 + j < nl) {
+                    const char *p = static_cast<const char *>(a.src[j0 + j]) + hb;
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const size_t v = base + (size_t)u * nthr;
+                        if (v < nvec) x[j][u] = cload_t<NT, V>(p + v * 16);
+                    }
+                }
+            }
+            if (pend >= 0) {
+                char *q = static_cast<char *>(a.dst[pend]) + hb;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const size_t v = base + (size_t)u * nthr;
+                    if (v < nvec) cstore_t<NT, V>(q + v * 16, acc[u]);
+                }
+                pend = -1;
+            }
+#pragma unroll
+            for (int j = 0; j < kFoldChunk; ++j) {
+                const int k = j0 + j;
+                if (k < nl) {
+                    if (k == 0) {
+#pragma unroll
+                        for (int u = 0; u < U; ++u) acc[u] = x[0][u];
+                    } else {
+#pragma unroll
+                        for (int u = 0; u < U; ++u)
+#pragma unroll
+                            for (int e = 0; e < EPV; ++e) acc[u].e[e] = rule<F, THREE>(x[j][u].e[e], acc[u].e[e]);
+                    }
+                    // exclusive: x_{k+1} is loaded when it shares this chunk; when there is none
+                    // (k + 1 == nl) the destination aliases no input that is read
+                    if (!ex || j + 1 < kFoldChunk || k + 1 >= nl) {
+                        char *q = static_cast<char *>(a.dst[k + ex]) + hb;
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const size_t v = base + (size_t)u * nthr;
+                            if (v < nvec) cstore_t<NT, V>(q + v * 16, acc[u]);
+                        }
+                    } else {
+                        pend = k + ex;
+                    }
+                }
+            }
+        }
+    }
+
+    const size_t t0 = a.head + nvec * EPV;
+    for (size_t i = t0 + tid; i < a.n; i += nthr) scan_scalar<F, THREE>(a, nl, i);
 }
 
 // ------------------------------------------------------------------ ring order, whole vector
@@ -375,6 +476,49 @@ template <class F> static int launch_fold(FoldArgs a, hipStream_t s)
     return MI355X_SUCCESS;
 }
 
+template <class F> static int launch_scan(ScanArgs a, hipStream_t s)
+{
+    using T = typename F::T;
+    constexpr size_t EPV = 16 / sizeof(T);
+    const int ex = a.exclusive ? 1 : 0, nl = a.nr - ex;
+    if (a.n == 0 || nl <= 0) return MI355X_SUCCESS;
+    if (a.nr > kMaxRanks) return set_error(MI355X_ERR_UNSUPPORTED, "scan over more than %d ranks", kMaxRanks);
+    // the pointers the kernel touches: sources 0..nl-1, destinations ex..nr-1
+    const uintptr_t m = (uintptr_t)a.src[0] & 15;
+    bool co = (m % sizeof(T)) == 0;
+    for (int j = 0; j < nl && co; ++j) co = (((uintptr_t)a.src[j]) & 15) == m;
+    for (int d = ex; d < a.nr && co; ++d) co = (((uintptr_t)a.dst[d]) & 15) == m;
+    if (co) {
+        size_t head = m ? (16 - m) / sizeof(T) : 0;
+        if (head > a.n) head = a.n;
+        a.head = head;
+        a.nvec = (a.n - head) / EPV;
+    } else {
+        a.head = a.n;
+        a.nvec = 0;
+    }
+    constexpr int U = 2;
+    size_t work = a.nvec ? (a.nvec + U - 1) / U : 0;
+    const size_t scalar = a.n - a.nvec * EPV;
+    if (scalar > work) work = scalar;
+    const size_t blocks = grid_for(work, coll_tune().blocks_per_cu);
+    const bool nt = (size_t)(2 * nl) * a.n * sizeof(T) > ((size_t)256 << 20);
+    bool three = false;
+    if constexpr (Op3Differs<F>::value) three = a.three != 0;
+    if (three) {
+        if constexpr (Op3Differs<F>::value) {
+            if (nt) hipLaunchKernelGGL((k_scan_part<F, U, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((k_scan_part<F, U, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        }
+    } else if (nt) {
+        hipLaunchKernelGGL((k_scan_part<F, U, true, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    } else {
+        hipLaunchKernelGGL((k_scan_part<F, U, false, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    }
+    MI_HIP(hipGetLastError());
+    return MI355X_SUCCESS;
+}
+
 template <class F> static int launch_ring_all(const RingAllArgs &a, hipStream_t s)
 {
     if (a.count == 0) return MI355X_SUCCESS;
@@ -459,6 +603,7 @@ struct CollSlot {
     int (*fold)(FoldArgs, hipStream_t) = nullptr;
     int (*tree)(const TreeArgs &, hipStream_t) = nullptr;
     int (*ring_all)(const RingAllArgs &, hipStream_t) = nullptr;
+    int (*scan)(ScanArgs, hipStream_t) = nullptr;
 };
 
 struct CollTable {
@@ -470,6 +615,7 @@ struct CollTable {
             s[op][ty].fold = &launch_fold<F>;
             s[op][ty].tree = &launch_tree<F>;
             s[op][ty].ring_all = &launch_ring_all<F>;
+            s[op][ty].scan = &launch_scan<F>;
         });
     }
 };
@@ -487,6 +633,13 @@ int launch_fold_slot(int op, int type, const FoldArgs &a, hipStream_t s)
     const CollSlot *sl = cslot(op, type);
     if (!sl) return set_error(MI355X_ERR_UNSUPPORTED, "no device fold for op %d type %d", op, type);
     return sl->fold(a, s);
+}
+
+int launch_scan_slot(int op, int type, const ScanArgs &a, hipStream_t s)
+{
+    const CollSlot *sl = cslot(op, type);
+    if (!sl) return set_error(MI355X_ERR_UNSUPPORTED, "no device scan for op %d type %d", op, type);
+    return sl->scan(a, s);
 }
 
 int launch_ring_all_slot(int op, int type, const RingAllArgs &a, hipStream_t s)

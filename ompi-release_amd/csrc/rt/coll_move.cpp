@@ -15,7 +15,8 @@
 // coll_basic_exscan.c:40-110): rank r's result is ((x0 op x1) op ...) op x_r, each step
 // ompi_op_reduce(op, partial, x_k) -- the partial is the `in` operand -- so rank r evaluates that
 // left fold over the n inputs directly (k_fold, order 0..r, every step role `in`), bit-identical
-// to the chain without its n-1 sequential hops.
+// to the chain without its n-1 sequential hops.  Large messages are partitioned instead
+// (scan_part): rank q evaluates ring block q of every rank's prefix in one pass (k_scan_part).
 #include <cstring>
 
 #include "comm_internal.hpp"
@@ -210,10 +211,91 @@ static int alltoallv_impl(mi355x_comm *c, const void *sbuf, const size_t *scount
     return finish(c, s);
 }
 
+// The partitioned flow's layout (host only; shared with the tests): owner q evaluates ring block q
+// = elements [src_off, src_off + len) of every prefix.  Rank q's own prefix goes straight into its
+// rbuf (slot_off = SIZE_MAX for r == q); rank r's sits in q's scratch at element slot_off: n - 1
+// slots of len elements, rank r's at index r (r < q) or r - 1 (r > q).
+static void scan_part_plan(size_t count, int n, int q, int r, size_t *src_off, size_t *len, size_t *slot_off)
+{
+    ring_block(count, n, q, src_off, len);
+    *slot_off = r == q ? SIZE_MAX : (size_t)(r < q ? r : r - 1) * *len;
+}
+
+// MPI_Scan / MPI_Exscan, owner-computes: rank q evaluates block q of EVERY
+// rank's prefix in one k_scan_part launch over the mapped inputs -- its own prefix into its rbuf,
+// the others' into its scratch (local writes only) -- and after the meeting point every rank pulls
+// its n - 1 other blocks out of the owners' scratch (k_multicopy, one segment per owner).  Each
+// input element is read once across the communicator instead of up to n times by the last rank,
+// and the bits are the chain's: a prefix is a chain, so the running accumulator of element i is
+// rank k's result after step k.  In place needs no extra copy: owner q is the only reader of
+// block q of anybody's input, and it is done before the meeting point that precedes the pulls.
+// *staged: a buffer cannot be exported -- nothing was done, the caller takes the chain flow.
+static int scan_part(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, bool exclusive,
+                     bool three, hipStream_t s, bool *staged)
+{
+    const size_t esz = mi355x_type_size(type);
+    const int n = c->size, me = c->rank;
+    size_t off, len, so;
+    scan_part_plan(count, n, me, me, &off, &len, &so);
+    int rc;
+    if (len) {
+        rc = ensure_scratch(c, (size_t)(n - 1) * len * esz);
+        if (rc) return rc;
+    }
+    MI_HIP(hipStreamSynchronize(s));
+    const void *mine[2] = {in, len ? c->scratch : nullptr};
+    const uint64_t sig[4] = {exclusive ? 27u : 26u, count, ((uint64_t)type << 32) | (uint64_t)op, three ? 1u : 0u};
+    std::vector<std::vector<void *>> P;
+    rc = exchange(c, 2, mine, sig, P, staged);
+    if (rc || *staged) return rc;
+    c->last_alg = 2;
+    if (len) {  // phase 1: block `me` of every prefix
+        ScanArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.nr = n;
+        a.exclusive = exclusive ? 1 : 0;
+        a.three = three ? 1 : 0;
+        a.n = len;
+        for (int k = 0; k < n; ++k) {
+            size_t o, l, slot;
+            scan_part_plan(count, n, me, k, &o, &l, &slot);
+            a.src[k] = (const char *)P[0][k] + off * esz;
+            a.dst[k] = k == me ? (char *)rbuf + off * esz : (char *)c->scratch + slot * esz;
+        }
+        rc = launch_scan_slot(op, type, a, s);
+        if (rc) return rc;
+    }
+    rc = finish(c, s);  // every owner is done with every input and has its prefixes in place
+    if (rc) return rc;
+    if (!(exclusive && me == 0)) {  // phase 2: my prefix's other blocks, from their owners
+        MultiCopyArgs m;
+        std::memset(&m, 0, sizeof(m));
+        for (int k = 1; k < n; ++k) {
+            const int q = (me + k) % n;
+            size_t qo, ql, slot;
+            scan_part_plan(count, n, q, me, &qo, &ql, &slot);
+            if (ql == 0) continue;
+            if (m.nseg == kMaxSegs) {  // (more owners than one launch holds: split the pull)
+                rc = copy_segments(m, s);
+                if (rc) return rc;
+                std::memset(&m, 0, sizeof(m));
+            }
+            add_seg(m, (const char *)P[1][q] + slot * esz, (char *)rbuf + qo * esz, ql * esz);
+        }
+        rc = copy_segments(m, s);
+        if (rc) return rc;
+    }
+    return finish(c, s);  // the owners keep their scratch until everybody has pulled
+}
+
 // MPI_Scan (exclusive = false) / MPI_Exscan (true) in coll/basic's order (see the file header).
 // sbuf NULL = MPI_IN_PLACE.  Exscan leaves rank 0's rbuf untouched.
+// three: coll/libnbc's form of the same chain (MPI_Iscan / MPI_Iexscan under NB_ORDER = 1,
+// nbc_iscan.c:89-105, nbc_iexscan.c:94-135): every step op3(in1 = own data, in2 = the partial).
+// Messages of at least scan_part_min bytes per rank take the partitioned flow (scan_part) when
+// the slot has a fold kernel and the buffers can be mapped; everything else the chain below.
 static int scan_impl(mi355x_comm *c, const void *sbuf, void *rbuf, size_t count, int type, int op, bool exclusive,
-                     void *stream)
+                     void *stream, bool three = false)
 {
     int rc = check_common(c, op, type);
     if (rc) return rc;
@@ -226,7 +308,12 @@ static int scan_impl(mi355x_comm *c, const void *sbuf, void *rbuf, size_t count,
     const void *in = sbuf ? sbuf : rbuf;
     const int last = exclusive ? me - 1 : me;   // fold over ranks 0..last
     if (!coll_slot_supported(op, type)) {  // (no fold kernel carries the slot: gather-then-fold, coll_gfold.cpp)
-        return gfold_scan(c, in, rbuf, count, type, op, last, s);
+        return gfold_scan(c, in, rbuf, count, type, op, last, s, three);
+    }
+    if (c->size > 1 && c->scan_part_min && count * esz >= c->scan_part_min) {
+        bool staged = false;
+        rc = scan_part(c, in, rbuf, count, type, op, exclusive, three, s, &staged);
+        if (rc || !staged) return rc;
     }
     // in place, rbuf is also an input the later ranks read: the result goes to scratch first
     const bool via_scratch = !sbuf && last >= 0 && !(last == 0 && me == 0);
@@ -253,6 +340,7 @@ static int scan_impl(mi355x_comm *c, const void *sbuf, void *rbuf, size_t count,
         pr.is_fold = true;
         for (int q = 0; q <= last; ++q) pr.order.push_back(q);
         pr.role_mask = 0;   // ompi_op_reduce(op, partial, x_k): the partial is `in`
+        pr.three = three;   // (libnbc: op(recvbuf = partial, sendbuf = x_k) -> in1 = x_k, in2 = partial)
         pr.nr = last + 1;
         std::vector<void *> dst(1, target);
         rc = run_program(op, type, pr, P[0], dst, 0, count, s);
@@ -369,7 +457,25 @@ int mi355x_iscan(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count, i
 {
     int rc = check_common(c, op, type);
     if (rc) return rc;
-    return post(c, stream, [=](hipStream_t s) { return scan_impl(c, sbuf, rbuf, count, type, op, false, s); }, req);
+    const bool three = c->nb_order != 0;  // coll/libnbc's order (scan_impl)
+    return post(c, stream, [=](hipStream_t s) { return scan_impl(c, sbuf, rbuf, count, type, op, false, s, three); }, req);
+}
+
+int mi355x_iexscan(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type, int op, void *stream,
+                   mi355x_request_t **req)
+{
+    int rc = check_common(c, op, type);
+    if (rc) return rc;
+    const bool three = c->nb_order != 0;
+    return post(c, stream, [=](hipStream_t s) { return scan_impl(c, sbuf, rbuf, count, type, op, true, s, three); }, req);
+}
+
+int mi355x_scan_part_plan(size_t count, int n, int q, int r, size_t *src_off, size_t *len, size_t *slot_off)
+{
+    if (n < 1 || n > kMaxRanks || q < 0 || q >= n || r < 0 || r >= n || !src_off || !len || !slot_off)
+        return set_error(MI355X_ERR_ARG, "bad scan plan arguments");
+    scan_part_plan(count, n, q, r, src_off, len, slot_off);
+    return MI355X_SUCCESS;
 }
 
 int mi355x_ialltoall(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, void *stream,

@@ -47,7 +47,9 @@ constexpr int kMaxBufs = 3;
 // dead peer is found by its pid and start time (peer_gone), not by a timeout; the bound only turns a
 // hang into an error eventually (tests set seconds)
 constexpr double kDefaultTimeoutS = 86400.0;
-constexpr int kVoteRing = 64;    // buffer-kind votes a rank keeps (mi355x_comm_vote)
+// default of MI355X_KNOB_SCAN_PART_MIN_BYTES; measured, see BASELINE.md ("Partitioned scan")
+constexpr size_t kScanPartMinDefault = 0;
+constexpr int kVoteRing = 64;   // buffer-kind votes a rank keeps (mi355x_comm_vote)
 constexpr int kVoteWindow = 32;  // calls per vote window: every rank waits at each window's last call
 
 struct BufDesc {
@@ -441,6 +443,9 @@ struct mi355x_comm {
     // MI355X_KNOB_NB_ORDER (env MI355X_NB_ORDER): 1 = iallreduce / ireduce / ireduce_scatter_block
     // run coll/libnbc's selection and operand order (coll_nbc.cpp); 0 = coll/tuned's, as the blocking calls
     int nb_order = 0;
+    // MI355X_KNOB_SCAN_PART_MIN_BYTES (env MI355X_SCAN_PART_MIN_BYTES): scan / exscan calls of at least
+    // this many bytes per rank take the partitioned flow (coll_move.cpp: scan_part); 0 = never
+    size_t scan_part_min = mi355x::kScanPartMinDefault;
     int last_alg = -1;
     double timeout_s = mi355x::kDefaultTimeoutS;
     bool time_phases = false;                     // MI355X_KNOB_TIME_PHASES
