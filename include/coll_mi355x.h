@@ -5,7 +5,7 @@
  * coll/tuned (30) and coll/cuda (78) -- for intra-communicators whose ranks all live on this
  * node.  It provides allreduce, reduce, reduce_scatter, reduce_scatter_block, allgather, bcast,
  * gather(v), scatter(v), allgatherv, alltoall(v), scan and exscan, and the nonblocking iallreduce,
- * ireduce, ireduce_scatter_block, iallgather, ibcast, iscan and iexscan; every other slot (alltoallw, barrier,
+ * ireduce, ireduce_scatter_block, ireduce_scatter, iallgather, ibcast, iscan and iexscan; every other slot (alltoallw, barrier,
  * the other nonblocking and neighborhood ones) stays with the lower-priority modules.  Entry points have exactly the reference
  * signatures (coll.h:181-239) and replace, for device buffers:
  *   mca_coll_cuda_allreduce            (ompi/mca/coll/cuda/coll_cuda_allreduce.c:30-77)
@@ -57,6 +57,9 @@ int mca_coll_mi355x_ireduce(void *sbuf, void *rbuf, int count, struct ompi_datat
 int mca_coll_mi355x_ireduce_scatter_block(void *sbuf, void *rbuf, int rcount, struct ompi_datatype_t *dtype,
                                           struct ompi_op_t *op, struct ompi_communicator_t *comm,
                                           ompi_request_t **request, mca_coll_base_module_t *module);
+int mca_coll_mi355x_ireduce_scatter(void *sbuf, void *rbuf, int *rcounts, struct ompi_datatype_t *dtype,
+                                    struct ompi_op_t *op, struct ompi_communicator_t *comm, ompi_request_t **request,
+                                    mca_coll_base_module_t *module);
 int mca_coll_mi355x_iallgather(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
                                struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
                                ompi_request_t **request, mca_coll_base_module_t *module);

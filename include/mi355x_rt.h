@@ -258,7 +258,8 @@ enum mi355x_knob {
                                            1 the device setup's (LL, pipelined), 2 also the service's */
     MI355X_KNOB_NB_ORDER = 44,          /* (per communicator, same value on every rank; env MI355X_NB_ORDER at
                                            creation; default 0) operand order of mi355x_iallreduce / _ireduce /
-                                           _ireduce_scatter_block: 0 = coll/tuned's, as the blocking calls; 1 =
+                                           _ireduce_scatter_block / _ireduce_scatter: 0 = coll/tuned's, as the
+                                           blocking calls; 1 =
                                            coll/libnbc's, the component that serves them in the reference (its
                                            own selection, every step the 3-buff rule with the rank's own data
                                            as in1); with 1 mi355x_iscan / _iexscan also run libnbc's form of
@@ -366,7 +367,7 @@ int mi355x_exscan(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t coun
  * goes straight into its rbuf). */
 int mi355x_scan_part_plan(size_t count, int n, int q, int r, size_t *src_off, size_t *len, size_t *slot_off);
 
-/* Nonblocking collectives (MPI_Iallreduce, MPI_Ireduce, MPI_Ireduce_scatter_block, MPI_Iallgather,
+/* Nonblocking collectives (MPI_Iallreduce, MPI_Ireduce, MPI_Ireduce_scatter_block, MPI_Ireduce_scatter, MPI_Iallgather,
  * MPI_Ibcast, MPI_Iscan, MPI_Iexscan; the coll framework's nonblocking slots, coll.h:241-356, served in the reference by
  * coll/libnbc: nbc_iallreduce.c etc.).  Each call is queued behind the caller's prior work on
  * `stream` and run, in posting order, by the communicator's progress thread.  Under
@@ -379,8 +380,13 @@ int mi355x_scan_part_plan(size_t count, int n, int q, int r, size_t *src_off, si
  * MI355X_ERR_UNSUPPORTED.  iscan and iexscan then run libnbc's form of the rank chain
  * (nbc_iscan.c:89-105, nbc_iexscan.c:94-135): the same shape as coll/basic's, every step the 3-buff
  * rule with the rank's own data as in1 and the received partial as in2, so only MAXLOC / MINLOC
- * change bits; iexscan leaves rank 0's rbuf untouched either way.  The other nonblocking calls do
- * not depend on the knob.  A blocking
+ * change bits; iexscan leaves rank 0's rbuf untouched either way.  ireduce_scatter (vector counts;
+ * sbuf NULL = MPI_IN_PLACE as in the blocking call; `rcounts` is copied at the post, and a NULL or
+ * negative count fails the post) gives the blocking mi355x_reduce_scatter's bits under NB_ORDER = 0,
+ * rules file and MI355X_KNOB_REDUCE_SCATTER_ALG included, and under NB_ORDER = 1 libnbc's binomial
+ * reduce of the whole vector to rank 0 + linear scatter (nbc_ireduce_scatter.c:37-164; 101, more
+ * than 16 ranks fail the post); a total count of 0 returns a completed request.  The other
+ * nonblocking calls do not depend on the knob.  A blocking
  * collective on the same communicator first waits for every posted one.  Requests: test (non-blocking; *done = 1 once finished, then returns the
  * collective's status), wait (blocks; returns the status), free (only once finished). */
 typedef struct mi355x_request mi355x_request_t;
@@ -390,6 +396,8 @@ int mi355x_ireduce(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t cou
                    void *stream, mi355x_request_t **req);
 int mi355x_ireduce_scatter_block(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t rcount, int type,
                                  int op, void *stream, mi355x_request_t **req);
+int mi355x_ireduce_scatter(mi355x_comm_t *comm, const void *sbuf, void *rbuf, const int *rcounts, int type,
+                           int op, void *stream, mi355x_request_t **req);
 int mi355x_iallgather(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes, void *stream,
                       mi355x_request_t **req);
 int mi355x_ibcast(mi355x_comm_t *comm, void *buf, size_t bytes, int root, void *stream, mi355x_request_t **req);
@@ -530,7 +538,7 @@ int mi355x_ddt_raw(const mi355x_ddt_t *d, size_t count, size_t *pos, int64_t *di
  * a given reference algorithm (layout documented in coll_comm.cpp).  For tests; no GPU needed. */
 int mi355x_sched_program(int kind, int n, int alg, int block, int *out, int cap);
 /* coll/libnbc's selection (101 binomial, 102 ring, 103 chain) for coll 0 = MPI_Iallreduce, 1 =
- * MPI_Ireduce, 2 = MPI_Ireduce_scatter_block of `bytes` bytes (the whole vector) over n ranks, and
+ * MPI_Ireduce, 2 = MPI_Ireduce_scatter_block, 3 = MPI_Ireduce_scatter of `bytes` bytes (the whole vector) over n ranks, and
  * segment e of its ring partition of `count` elements (nbc_iallreduce.c:311-329).  No GPU. */
 int mi355x_nbc_decision(int coll, int n, size_t bytes, int inplace);
 int mi355x_nbc_ring_block(size_t count, int n, int e, size_t *off, size_t *len);

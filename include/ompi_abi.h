@@ -541,6 +541,10 @@ typedef int (*mca_coll_base_module_ireduce_scatter_block_fn_t)(void *sbuf, void 
                                                                struct ompi_communicator_t *comm,
                                                                ompi_request_t **request,
                                                                mca_coll_base_module_t *module);
+typedef int (*mca_coll_base_module_ireduce_scatter_fn_t)(void *sbuf, void *rbuf, int *rcounts,
+                                                         struct ompi_datatype_t *dtype, struct ompi_op_t *op,
+                                                         struct ompi_communicator_t *comm, ompi_request_t **request,
+                                                         mca_coll_base_module_t *module);
 typedef int (*mca_coll_base_module_enable_fn_t)(mca_coll_base_module_t *module, struct ompi_communicator_t *comm);
 typedef int (*mca_coll_base_module_ft_event_fn_t)(int state);
 typedef void (*mca_coll_base_any_fn_t)(void);   /* slots the components never call */
@@ -575,7 +579,7 @@ struct mca_coll_base_module_2_0_0_t {
     mca_coll_base_module_iexscan_fn_t coll_iexscan;
     mca_coll_base_any_fn_t coll_igather, coll_igatherv;
     mca_coll_base_module_ireduce_fn_t coll_ireduce;
-    mca_coll_base_any_fn_t coll_ireduce_scatter;
+    mca_coll_base_module_ireduce_scatter_fn_t coll_ireduce_scatter;
     mca_coll_base_module_ireduce_scatter_block_fn_t coll_ireduce_scatter_block;
     mca_coll_base_module_iscan_fn_t coll_iscan;
     mca_coll_base_any_fn_t coll_iscatter, coll_iscatterv;
@@ -633,7 +637,8 @@ typedef struct mca_coll_base_comm_coll_t {
     struct { mca_coll_base_any_fn_t fn; mca_coll_base_module_t *module; } coll_igg[2];  /* igather(v) */
     mca_coll_base_module_ireduce_fn_t coll_ireduce;
     mca_coll_base_module_t *coll_ireduce_module;
-    struct { mca_coll_base_any_fn_t fn; mca_coll_base_module_t *module; } coll_ireduce_scatter_pair;
+    mca_coll_base_module_ireduce_scatter_fn_t coll_ireduce_scatter;
+    mca_coll_base_module_t *coll_ireduce_scatter_module;
     mca_coll_base_module_ireduce_scatter_block_fn_t coll_ireduce_scatter_block;
     mca_coll_base_module_t *coll_ireduce_scatter_block_module;
     mca_coll_base_module_iscan_fn_t coll_iscan;

@@ -40,6 +40,9 @@ OPS = ["NULL", "MAX", "MIN", "SUM", "PROD", "LAND", "BAND", "LOR", "BOR", "LXOR"
 OP = {name: i for i, name in enumerate(OPS)}
 
 MI355X_SUCCESS = 0
+# enum mi355x_status (mi355x_types.h): the names an MI355XError carries
+STATUS = {-1: "MI355X_ERR_ARG", -2: "MI355X_ERR_UNSUPPORTED", -3: "MI355X_ERR_HIP", -4: "MI355X_ERR_NOMEM",
+          -5: "MI355X_ERR_PEER", -6: "MI355X_ERR_TIMEOUT", -7: "MI355X_ERR_TRUNCATE"}
 
 
 class MI355XError(RuntimeError):
@@ -138,6 +141,7 @@ def _declare(lib: ctypes.CDLL) -> None:
         "mi355x_iallreduce": (i, [vp, vp, vp, sz, i, i, vp, c.POINTER(vp)]),
         "mi355x_ireduce": (i, [vp, vp, vp, sz, i, i, i, vp, c.POINTER(vp)]),
         "mi355x_ireduce_scatter_block": (i, [vp, vp, vp, sz, i, i, vp, c.POINTER(vp)]),
+        "mi355x_ireduce_scatter": (i, [vp, vp, vp, c.POINTER(i), i, i, vp, c.POINTER(vp)]),
         "mi355x_iallgather": (i, [vp, vp, vp, sz, vp, c.POINTER(vp)]),
         "mi355x_ibcast": (i, [vp, vp, sz, i, vp, c.POINTER(vp)]),
         "mi355x_request_test": (i, [vp, c.POINTER(i)]),
@@ -210,7 +214,7 @@ def _declare(lib: ctypes.CDLL) -> None:
 def check(rc: int, what: str = "") -> None:
     if rc != MI355X_SUCCESS:
         msg = rt().mi355x_last_error().decode(errors="replace")
-        raise MI355XError(f"{what} failed ({rc}): {msg}")
+        raise MI355XError(f"{what} failed ({rc} {STATUS.get(rc, '?')}): {msg}")
 
 
 def op_reduce(op: int, ty: int, src: int, inout: int, count: int, stream: int | None = None) -> None:
@@ -373,6 +377,11 @@ class Comm:
 
     def ireduce_scatter_block(self, sbuf, rbuf, rcount, ty, op, stream=None) -> Request:
         return self._post("mi355x_ireduce_scatter_block", sbuf, rbuf, rcount, ty, op, stream)
+
+    def ireduce_scatter(self, sbuf, rbuf, rcounts, ty, op, stream=None) -> Request:
+        """MPI_Ireduce_scatter; rcounts (a sequence, or a ctypes int array) is copied by the engine at the post"""
+        arr = rcounts if isinstance(rcounts, ctypes.Array) else (ctypes.c_int * len(rcounts))(*rcounts)
+        return self._post("mi355x_ireduce_scatter", sbuf, rbuf, arr, ty, op, stream)
 
     def iallgather(self, sbuf, rbuf, nbytes, stream=None) -> Request:
         return self._post("mi355x_iallgather", sbuf, rbuf, nbytes, stream)
@@ -674,7 +683,7 @@ def sched_program(kind: int, n: int, alg: int, block: int) -> list[int]:
 
 
 def nbc_decision(coll: int, n: int, nbytes: int, inplace: bool = False) -> int:
-    """coll/libnbc's algorithm (NBC_ALG) for coll 0 iallreduce, 1 ireduce, 2 ireduce_scatter_block"""
+    """coll/libnbc's algorithm (NBC_ALG) for coll 0 iallreduce, 1 ireduce, 2 ireduce_scatter_block, 3 ireduce_scatter"""
     k = rt().mi355x_nbc_decision(coll, n, nbytes, 1 if inplace else 0)
     check(0 if k >= 0 else k, "mi355x_nbc_decision")
     return k

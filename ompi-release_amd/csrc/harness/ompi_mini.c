@@ -429,6 +429,7 @@ void mini_comm_install(ompi_communicator_t *c, mca_coll_base_module_t *m)
     INST(ibcast)
     INST(ireduce)
     INST(ireduce_scatter_block)
+    INST(ireduce_scatter)
     INST(iscan)
     INST(iexscan)
     INST(gather)
@@ -490,6 +491,7 @@ void mini_comm_destroy(ompi_communicator_t *c)
     REL(ibcast)
     REL(ireduce)
     REL(ireduce_scatter_block)
+    REL(ireduce_scatter)
     REL(iscan)
     REL(iexscan)
     REL(gather)
@@ -859,6 +861,12 @@ int mini_iexscan(ompi_communicator_t *c, void *s, void *r, int n, ompi_datatype_
     return c->c_coll.coll_iexscan(s, r, n, d, op, c, req, c->c_coll.coll_iexscan_module);
 }
 
+int mini_ireduce_scatter(ompi_communicator_t *c, void *s, void *r, int *rcounts, ompi_datatype_t *d, ompi_op_t *op,
+                         ompi_request_t **req)
+{
+    return c->c_coll.coll_ireduce_scatter(s, r, rcounts, d, op, c, req, c->c_coll.coll_ireduce_scatter_module);
+}
+
 void *mini_comm_fn(ompi_communicator_t *c, int which)
 {
     switch (which) {
@@ -884,6 +892,7 @@ void *mini_comm_fn(ompi_communicator_t *c, int which)
     case 19: return (void *)c->c_coll.coll_exscan;
     case 20: return (void *)c->c_coll.coll_iscan;
     case 21: return (void *)c->c_coll.coll_iexscan;
+    case 22: return (void *)c->c_coll.coll_ireduce_scatter;
     default: return NULL;
     }
 }
@@ -1164,10 +1173,34 @@ static size_t span_of(const ompi_datatype_t *dt, size_t k)
     return k ? (size_t)(dt->super.true_ub + (ptrdiff_t)(k - 1) * (dt->super.ub - dt->super.lb)) : 0;
 }
 
+/* coll/libnbc's binomial tree to rank 0 (nbc_ireduce.c:229-282) over the slots' pieces: what virtual
+ * rank v holds when it sends -- its own piece, then per round own (op) received, the 3-buff step
+ * (ompi_3buff_op_reduce: target = in1 (op) in2, own data as in1) */
+static int host_binomial(struct mini_chan *ch, int n, int v, size_t off, size_t bytes, int m, char *out,
+                         ompi_datatype_t *dt, ompi_op_t *op)
+{
+    memcpy(out, chan_slot(ch, v) + off, bytes);
+    char *peer = NULL;
+    int rc = OMPI_SUCCESS;
+    for (int r = 1; rc == OMPI_SUCCESS && v % (1 << r) == 0 && (1 << (r - 1)) < n; ++r) {
+        const int p = v + (1 << (r - 1));
+        if (p >= n) continue;
+        if (!peer && !(peer = malloc(bytes + 1))) return OMPI_ERR_OUT_OF_RESOURCE;
+        rc = host_binomial(ch, n, p, off, bytes, m, peer, dt, op);
+        if (rc != OMPI_SUCCESS) break;
+        host_op_reduce(op, out, peer, m, dt);  /* peer = out (op) peer */
+        memcpy(out, peer, bytes);
+    }
+    free(peer);
+    return rc;
+}
+
+#define HOST_LINEAR (-1)
+#define HOST_BINOMIAL (-2)
 /* Reduce the ranks' `total`-instance contributions (src; NULL: contributes nothing -- never
  * happens in MPI, every rank contributes) over instances [lo, lo + cnt) into dst (cnt instances;
- * NULL: this rank only contributes).  chain < 0: linear order over all ranks; chain >= 0: the
- * scan chain over ranks 0..chain. */
+ * NULL: this rank only contributes).  chain == HOST_LINEAR: linear order over all ranks;
+ * HOST_BINOMIAL: libnbc's binomial tree to rank 0; chain >= 0: the scan chain over ranks 0..chain. */
 static int host_reduce(ompi_communicator_t *c, const char *src, size_t total, size_t lo, size_t cnt, int chain,
                        char *dst, ompi_datatype_t *dt, ompi_op_t *op)
 {
@@ -1191,6 +1224,7 @@ static int host_reduce(ompi_communicator_t *c, const char *src, size_t total, si
         free(inb);
         return OMPI_ERR_OUT_OF_RESOURCE;
     }
+    int berr = OMPI_SUCCESS;
     for (size_t c0 = 0; c0 < total || (total == 0 && c0 == 0); c0 += per) {
         if (total == 0) break;
         const size_t k = total - c0 < per ? total - c0 : per;
@@ -1199,7 +1233,10 @@ static int host_reduce(ompi_communicator_t *c, const char *src, size_t total, si
         const size_t a = c0 > lo ? c0 : lo, b = (c0 + k < lo + cnt) ? c0 + k : lo + cnt;
         if (dst && a < b) {
             const size_t off = (a - c0) * ext, m = b - a, bytes = span_of(dt, m);
-            if (chain < 0) {
+            if (chain == HOST_BINOMIAL) {
+                const int e = host_binomial(ch, n, 0, off, bytes, (int)m, acc, dt, op);
+                if (e != OMPI_SUCCESS) berr = e;
+            } else if (chain < 0) {
                 memcpy(acc, chan_slot(ch, n - 1) + off, bytes);
                 for (int i = n - 2; i >= 0; --i) {
                     memcpy(inb, chan_slot(ch, i) + off, bytes);
@@ -1222,7 +1259,7 @@ static int host_reduce(ompi_communicator_t *c, const char *src, size_t total, si
     free(acc);
     free(tmp);
     free(inb);
-    return OMPI_SUCCESS;
+    return berr;
 }
 
 /* root's `total` instances to every rank, slot-sized pieces through the root's slot */
@@ -1285,9 +1322,10 @@ static int h_reduce(void *s, void *r, int n, struct ompi_datatype_t *d, struct o
     return rc;
 }
 
-/* reduce_scatter(_block): my block of the linear reduction (coll/basic reduces to 0 and scatters) */
+/* reduce_scatter(_block): my block of the linear reduction (coll/basic reduces to 0 and scatters);
+ * order HOST_BINOMIAL: of libnbc's binomial reduction to 0 (MPI_Ireduce_scatter, nbc_ireduce_scatter.c:84-152) */
 static int h_rs_common(void *s, void *r, const int *counts, int rcount, struct ompi_datatype_t *d, struct ompi_op_t *o,
-                       struct ompi_communicator_t *c)
+                       struct ompi_communicator_t *c, int order)
 {
     const int n = c->c_local_group->grp_proc_count, me = c->c_my_rank;
     size_t total = 0, lo = 0;
@@ -1306,7 +1344,7 @@ static int h_rs_common(void *s, void *r, const int *counts, int rcount, struct o
         memcpy(copy, r, span_of(d, total));
         src = copy;
     }
-    const int rc = host_reduce(c, src, total, lo, mine, -1, (char *)r, d, o);
+    const int rc = host_reduce(c, src, total, lo, mine, order, (char *)r, d, o);
     free(copy);
     return rc;
 }
@@ -1317,7 +1355,7 @@ static int h_rsb(void *s, void *r, int n, struct ompi_datatype_t *d, struct ompi
     (void)m;
     host_calls[1]++;
     if (guard("reduce_scatter_block", 2, s, r)) return MINI_ERR_DEVICE_BUFFER;
-    return h_rs_common(s, r, NULL, n, d, o, c);
+    return h_rs_common(s, r, NULL, n, d, o, c, HOST_LINEAR);
 }
 
 static int h_rs(void *s, void *r, int *counts, struct ompi_datatype_t *d, struct ompi_op_t *o,
@@ -1326,7 +1364,7 @@ static int h_rs(void *s, void *r, int *counts, struct ompi_datatype_t *d, struct
     (void)m;
     host_calls[2]++;
     if (guard("reduce_scatter", 2, s, r)) return MINI_ERR_DEVICE_BUFFER;
-    return h_rs_common(s, r, counts, 0, d, o, c);
+    return h_rs_common(s, r, counts, 0, d, o, c, HOST_LINEAR);
 }
 
 static int h_scan_common(int exclusive, void *s, void *r, int n, struct ompi_datatype_t *d, struct ompi_op_t *o,
@@ -1465,9 +1503,10 @@ static int h_alltoall(void *s, int sc, struct ompi_datatype_t *sd, void *r, int 
 /* ---- nonblocking: queued, run in posting order from the progress callback */
 typedef struct mini_hreq {
     ompi_request_t super;
-    int kind;  /* 0 allreduce, 1 reduce, 2 rsb, 3 allgather, 4 bcast, 5 scan, 6 exscan */
+    int kind;  /* 0 allreduce, 1 reduce, 2 rsb, 3 allgather, 4 bcast, 5 scan, 6 exscan, 7 reduce_scatter */
     void *s, *r;
     int n, n2, root;
+    int *counts;  /* kind 7: the request's own copy of recvcounts (freed once it has run) */
     struct ompi_datatype_t *d, *d2;
     struct ompi_op_t *o;
     struct ompi_communicator_t *c;
@@ -1504,6 +1543,11 @@ static int hq_progress(void)
         case 3: rc = h_allgather(q->s, q->n, q->d, q->r, q->n2, q->d2, q->c, NULL); break;
         case 5: rc = h_scan(q->s, q->r, q->n, q->d, q->o, q->c, NULL); break;
         case 6: rc = h_exscan(q->s, q->r, q->n, q->d, q->o, q->c, NULL); break;
+        case 7:
+            rc = h_rs_common(q->s, q->r, q->counts, 0, q->d, q->o, q->c, HOST_BINOMIAL);
+            free(q->counts);
+            q->counts = NULL;
+            break;
         default: rc = h_bcast(q->r, q->n, q->d, q->root, q->c, NULL); break;
         }
         q->super.req_status.MPI_ERROR = rc;
@@ -1563,6 +1607,24 @@ static int h_irsb(void *s, void *r, int n, struct ompi_datatype_t *d, struct omp
     if (guard("ireduce_scatter_block", 2, s, r)) return MINI_ERR_DEVICE_BUFFER;
     return hq_post((mini_hreq_t){.kind = 2, .s = s, .r = r, .n = n, .d = d, .o = o, .c = c}, req);
 }
+/* MPI_Ireduce_scatter as coll/libnbc, the slot's owner in the reference, orders it: the binomial
+ * reduce to rank 0 + scatter (the counts are copied: MPI lets the caller reuse its array once the
+ * call has returned) */
+static int h_irs(void *s, void *r, int *counts, struct ompi_datatype_t *d, struct ompi_op_t *o,
+                 struct ompi_communicator_t *c, ompi_request_t **req, mca_coll_base_module_t *m)
+{
+    (void)m;
+    host_calls[17]++;
+    if (guard("ireduce_scatter", 2, s, r)) return MINI_ERR_DEVICE_BUFFER;
+    if (!counts) return OMPI_ERR_BAD_PARAM;
+    const size_t n = (size_t)c->c_local_group->grp_proc_count;
+    int *copy = malloc(n * sizeof(int));
+    if (!copy) return OMPI_ERR_OUT_OF_RESOURCE;
+    memcpy(copy, counts, n * sizeof(int));
+    const int rc = hq_post((mini_hreq_t){.kind = 7, .s = s, .r = r, .counts = copy, .d = d, .o = o, .c = c}, req);
+    if (rc != OMPI_SUCCESS) free(copy);
+    return rc;
+}
 static int h_iscan(void *s, void *r, int n, struct ompi_datatype_t *d, struct ompi_op_t *o,
                    struct ompi_communicator_t *c, ompi_request_t **req, mca_coll_base_module_t *m)
 {
@@ -1614,6 +1676,7 @@ mca_coll_base_module_t *mini_host_module(void)
     m->coll_iallreduce = h_iallreduce;
     m->coll_ireduce = h_ireduce;
     m->coll_ireduce_scatter_block = h_irsb;
+    m->coll_ireduce_scatter = h_irs;
     m->coll_iallgather = h_iallgather;
     m->coll_iscan = h_iscan;
     m->coll_iexscan = h_iexscan;

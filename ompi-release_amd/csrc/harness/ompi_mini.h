@@ -41,7 +41,9 @@ int mini_bcast(ompi_communicator_t *c, void *b, int n, ompi_datatype_t *d, int r
 int mini_iscan(ompi_communicator_t *c, void *s, void *r, int n, ompi_datatype_t *d, ompi_op_t *op, ompi_request_t **req);
 int mini_iexscan(ompi_communicator_t *c, void *s, void *r, int n, ompi_datatype_t *d, ompi_op_t *op,
                  ompi_request_t **req);
-void *mini_comm_fn(ompi_communicator_t *c, int which);  /* 20 / 21: the iscan / iexscan slots */
+int mini_ireduce_scatter(ompi_communicator_t *c, void *s, void *r, int *rcounts, ompi_datatype_t *d, ompi_op_t *op,
+                         ompi_request_t **req);
+void *mini_comm_fn(ompi_communicator_t *c, int which);  /* 20 / 21: the iscan / iexscan slots; 22: ireduce_scatter */
 mca_coll_base_module_t *mini_stub_module(void);
 int mini_stub_calls(int which);
 int mini_stub_marker(void);

@@ -65,6 +65,8 @@ typedef struct mca_coll_mi355x_module_t {
     mca_coll_base_module_t *prev_ireduce_module;
     mca_coll_base_module_ireduce_scatter_block_fn_t prev_ireduce_scatter_block;
     mca_coll_base_module_t *prev_ireduce_scatter_block_module;
+    mca_coll_base_module_ireduce_scatter_fn_t prev_ireduce_scatter;
+    mca_coll_base_module_t *prev_ireduce_scatter_module;
     mca_coll_base_module_iallgather_fn_t prev_iallgather;
     mca_coll_base_module_t *prev_iallgather_module;
     mca_coll_base_module_ibcast_fn_t prev_ibcast;
@@ -113,6 +115,7 @@ static void module_destruct(opal_object_t *o)
     release_prev(m->prev_iexscan_module);
     release_prev(m->prev_ireduce_module);
     release_prev(m->prev_ireduce_scatter_block_module);
+    release_prev(m->prev_ireduce_scatter_module);
     release_prev(m->prev_iallgather_module);
     release_prev(m->prev_ibcast_module);
     for (int i = 0; i < 8; ++i)
@@ -1434,7 +1437,9 @@ static int nb_host_join(mca_coll_mi355x_module_t *m, void *sbuf, void *rbuf, int
     memset(st, 0, sizeof(*st));
     *sd = inplace ? NULL : sbuf;
     *rd = rsig ? rbuf : NULL;
-    const size_t rspan = inplace ? in_bytes : out_bytes;
+    /* (never 0: the engine takes sbuf == rbuf for MPI_IN_PLACE, and a rank that receives nothing -- a
+     * zero count of MPI_Ireduce_scatter -- would alias its two copies and alone take the in-place flow) */
+    const size_t rspan = inplace ? in_bytes : (out_bytes ? out_bytes : 16);
     const size_t a = (rh ? rspan : 0) + (sh ? in_bytes : 0);
     if (mi355x_malloc(&st->stage, a ? a : 1) != MI355X_SUCCESS) return MI355X_ERR_NOMEM;
     int rc = MI355X_SUCCESS;
@@ -1574,6 +1579,45 @@ int mca_coll_mi355x_ireduce_scatter_block(void *sbuf, void *rbuf, int rcount, st
     const size_t in = dt_span(dtype, (size_t)rcount * (size_t)mi355x_comm_size_of(comm));
     const size_t out = dt_span(dtype, (size_t)rcount);
     NB_STAGED(ireduce_scatter_block, in, inplace ? in : out, inplace, out, dtype, sbuf, rbuf, rcount, dtype, op, comm);
+}
+
+/* MPI_Ireduce_scatter (vector counts): in the reference coll/libnbc's, whose schedule receives into a
+ * host tmpbuf and reduces it with sendbuf (nbc_ireduce_scatter.c:87-111) -- not usable on device
+ * buffers.  Shaped like ireduce_scatter_block above: the input spans the whole vector, the output
+ * this rank's count (0 for a rank that receives nothing); the engine copies rcounts at the post. */
+int mca_coll_mi355x_ireduce_scatter(void *sbuf, void *rbuf, int *rcounts, struct ompi_datatype_t *dtype,
+                                    struct ompi_op_t *op, struct ompi_communicator_t *comm, ompi_request_t **request,
+                                    mca_coll_base_module_t *module)
+{
+    mca_coll_mi355x_module_t *m = MOD(module);
+    const int inplace = (sbuf == MPI_IN_PLACE);
+    const int t = reducible_type(dtype);
+    const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm);
+    size_t total = 0;
+    for (int q = 0; q < n; ++q) {
+        if (!rcounts || rcounts[q] < 0) NB_FALLBACK(ireduce_scatter, sbuf, rbuf, rcounts, dtype, op, comm, request);
+        total += (size_t)rcounts[q];
+    }
+    const size_t in = dt_span(dtype, total), out = dt_span(dtype, (size_t)rcounts[me]);
+    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
+    if (!engine_op(op, t) || (!dev && !m->mixed))
+        NB_STAGED(ireduce_scatter, in, inplace ? in : out, inplace, out, dtype, sbuf, rbuf, rcounts, dtype, op, comm);
+    mi355x_request_t *eng = NULL;
+    if (!dev) {  /* host buffers: join the engine on device copies (nb_host_join) */
+        const size_t esz = mi355x_type_size(t);
+        struct nb_stage st;
+        void *sd, *rd;
+        int rc = nb_host_join(m, sbuf, rbuf, inplace, total * esz, (size_t)rcounts[me] * esz, 1, &sd, &rd, &st);
+        if (rc == MI355X_SUCCESS)
+            rc = mi355x_ireduce_scatter(m->engine, sd, rd, rcounts, t, op->o_f_to_c_index, NULL, &eng);
+        if (rc == MI355X_SUCCESS) return nb_start_full(eng, comm, request, 0, &st);
+        nb_stage_release(&st);
+        if (!NB_UNFIT(rc)) return map_rc(rc);
+    } else {
+        int rc = mi355x_ireduce_scatter(m->engine, inplace ? NULL : sbuf, rbuf, rcounts, t, op->o_f_to_c_index, NULL, &eng);
+        if (!NB_UNFIT(rc)) return rc ? map_rc(rc) : nb_start(eng, comm, request);
+    }
+    NB_STAGED(ireduce_scatter, in, inplace ? in : out, inplace, out, dtype, sbuf, rbuf, rcounts, dtype, op, comm);
 }
 
 /* MPI_Iscan / MPI_Iexscan: in the reference coll/libnbc's, whose schedule copies through a host
@@ -2268,6 +2312,7 @@ static int module_enable(mca_coll_base_module_t *module, struct ompi_communicato
     SNAP_OPT(iallreduce);
     SNAP_OPT(ireduce);
     SNAP_OPT(ireduce_scatter_block);
+    SNAP_OPT(ireduce_scatter);
     SNAP_OPT(iallgather);
     SNAP_OPT(ibcast);
     SNAP_OPT(iscan);
@@ -2382,7 +2427,8 @@ static int component_register(void)
     register_int("selftest", "Run the cross-device flows' self-tests at a communicator's first device-buffer collective "
                  "(a flow that fails on any rank is turned off on every rank); 0 = trust every flow", OPAL_INFO_LVL_9,
                  &mca_coll_mi355x_selftest);
-    register_int("nb_order", "Operand order of MPI_Iallreduce / MPI_Ireduce / MPI_Ireduce_scatter_block in the engine: "
+    register_int("nb_order", "Operand order of MPI_Iallreduce / MPI_Ireduce / MPI_Ireduce_scatter_block / "
+                 "MPI_Ireduce_scatter in the engine: "
                  "0 = coll/tuned's, as the blocking calls; 1 = coll/libnbc's, the component that serves them otherwise "
                  "(a libnbc tree the device cannot hold goes to that component)", OPAL_INFO_LVL_6,
                  &mca_coll_mi355x_nb_order);
@@ -2447,6 +2493,7 @@ static mca_coll_base_module_t *component_comm_query(struct ompi_communicator_t *
     m->super.coll_iexscan = mca_coll_mi355x_iexscan;
     m->super.coll_ireduce = mca_coll_mi355x_ireduce;
     m->super.coll_ireduce_scatter_block = mca_coll_mi355x_ireduce_scatter_block;
+    m->super.coll_ireduce_scatter = mca_coll_mi355x_ireduce_scatter;
     m->super.coll_iallgather = mca_coll_mi355x_iallgather;
     m->super.coll_ibcast = mca_coll_mi355x_ibcast;
     m->super.ft_event = NULL;

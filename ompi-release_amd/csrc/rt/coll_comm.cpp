@@ -642,7 +642,8 @@ int mi355x_comm_set(mi355x_comm_t *c, int knob, long value)
 // coll/libnbc's programs (coll_nbc.cpp), every step the 3-buff rule op3(in1 = out, in2 = in) -- the
 // layouts above with 2 added to the first int ([3, ...] fold, [2, ...] tree):
 // kind 6: iallreduce (alg 101 binomial, 102 ring segment `block`); kind 7: ireduce to rank `block`
-// (alg 101 binomial, 103 chain); kind 8: ireduce_scatter_block.
+// (alg 101 binomial, 103 chain); kind 8: ireduce_scatter_block; kind 9: ireduce_scatter (`block` = the
+// rank whose block it is; the ints of kind 8).
 // Returns the number of ints written or < 0.
 int mi355x_sched_program(int kind, int n, int alg, int block, int *out, int cap)
 {
@@ -667,7 +668,9 @@ int mi355x_sched_program(int kind, int n, int alg, int block, int *out, int cap)
     case 6:
     case 7:
     case 8:
+    case 9:
         if (block < 0 || block >= n) return set_error(MI355X_ERR_ARG, "bad block %d", block);
+        if (kind == 9) kind = 8;
         if (kind == 8) alg = NBC_BINOMIAL;
         if (alg != NBC_BINOMIAL && alg != (kind == 6 ? NBC_RING : NBC_CHAIN)) return set_error(MI355X_ERR_ARG, "bad algorithm %d", alg);
         ok = nbc_program(kind - 6, n, alg, block, &pr);

@@ -156,7 +156,7 @@ int gfold_reduce(mi355x_comm *c, const void *in, void *rbuf, size_t count, int t
 int gfold_reduce_scatter_block(mi355x_comm *c, const void *in, void *rbuf, size_t rcount, int type, int op,
                                hipStream_t s, bool nbc = false);
 int gfold_reduce_scatter(mi355x_comm *c, const void *in, void *rbuf, const size_t *disp, int type, int op,
-                         hipStream_t s);
+                         hipStream_t s, bool nbc = false);
 int gfold_scan(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, int last, hipStream_t s,
                bool three = false);
 hipStream_t setup_stream(mi355x_comm *c);
@@ -195,13 +195,14 @@ int reduce_scatter_block_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, si
 // coll_nbc.cpp
 int nbc_allreduce_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type, int op,
                        void *stream);
-// the reduce (root >= 0) or reduce_scatter_block (root < 0) program of libnbc for the call
+// the reduce (root >= 0) or reduce_scatter(_block) (root < 0) program of libnbc for the call
 bool nbc_reduce_program(const mi355x_comm *c, size_t count, size_t esz, int root, Program *pr, int *alg);
 // MI355X_SUCCESS, or MI355X_ERR_UNSUPPORTED when the call's libnbc program does not fit the device
-// (coll: 0 iallreduce, 1 ireduce, 2 ireduce_scatter_block; count = the whole vector's elements)
+// (coll: 0 iallreduce, 1 ireduce, 2 ireduce_scatter_block, 3 ireduce_scatter; count = the whole
+// vector's elements)
 int nbc_check(const mi355x_comm *c, int coll, size_t count, int type, bool inplace, int root);
 int reduce_scatter_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, const int *rcounts, int type,
-                          int op, void *stream);
+                          int op, void *stream, bool nbc = false);
 int allgather_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, void *stream);
 int bcast_impl(mi355x_comm_t *c, void *buf, size_t bytes, int root, void *stream);
 

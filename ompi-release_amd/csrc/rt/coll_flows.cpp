@@ -436,8 +436,11 @@ int reduce_scatter_block_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, si
 }
 
 // MPI_Reduce_scatter with vector counts (coll_tuned_reduce_scatter_intra_dec_fixed order)
+// nbc: coll/libnbc's binomial reduce of the whole vector to rank 0 + linear scatter by recvcounts
+// instead (MPI_Ireduce_scatter under NB_ORDER = 1, nbc_ireduce_scatter.c:37-164): per element the
+// program of MPI_Ireduce_scatter_block, never through the resident service.
 int reduce_scatter_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, const int *rcounts, int type,
-                          int op, void *stream)
+                          int op, void *stream, bool nbc)
 {
     int rc = check_common(c, op, type);
     if (rc) return rc;
@@ -453,18 +456,22 @@ int reduce_scatter_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, const in
     CallStream call_stream(c, s);  // (the setup work of this call, if any, runs on its stream)
     if (const int rs_ = dev_setup(c)) return rs_;  // (first device-buffer collective: collective setup)
     if (!coll_slot_supported(op, type)) {  // (no fold kernel carries the slot: gather-then-fold, coll_gfold.cpp)
-        return gfold_reduce_scatter(c, sbuf ? sbuf : rbuf, rbuf, disp.data(), type, op, s);
+        return gfold_reduce_scatter(c, sbuf ? sbuf : rbuf, rbuf, disp.data(), type, op, s, nbc);
     }
     const size_t esz = mi355x_type_size(type);
     const void *in = sbuf ? sbuf : rbuf;
-    const int alg = pick_reduce_scatter(c, count, esz);
+    const int alg = nbc ? (int)NBC_BINOMIAL : pick_reduce_scatter(c, count, esz);
     c->last_alg = alg;
     const size_t mine_n = (size_t)rcounts[c->rank];
-    const bool inplace = (in == (const void *)rbuf);
+    // MPI_IN_PLACE is all-or-none and decides the flow (the resident service is not taken in place), so
+    // every rank must answer alike: sbuf NULL, or the caller's two pointers equal -- but not on a rank
+    // that receives nothing, which writes no byte of rbuf and may hand in any pointer for it (a rank
+    // with a zero count and sbuf == rbuf would otherwise take the in-place flow alone)
+    const bool inplace = (in == (const void *)rbuf) && (!sbuf || mine_n > 0);
     {
         size_t mb = 0;
         for (int r = 0; r < c->size; ++r) mb = std::max(mb, (size_t)rcounts[r]);
-        rc = svc_maybe_claim(c, !inplace && c->svc_rs && mb * esz <= c->svc_pull_max);
+        rc = svc_maybe_claim(c, !nbc && !inplace && c->svc_rs && mb * esz <= c->svc_pull_max);
         if (rc) return rc;
     }
     if (inplace) {
@@ -475,7 +482,7 @@ int reduce_scatter_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, const in
     const void *mine[1] = {in};
     uint64_t h = 1469598103934665603ull;
     for (int r = 0; r < c->size; ++r) h = (h ^ (uint64_t)rcounts[r]) * 1099511628211ull;
-    const uint64_t sig[4] = {3, h, (uint64_t)type, (uint64_t)op};
+    const uint64_t sig[4] = {nbc ? 103u : 3u, h, (uint64_t)type, (uint64_t)op};
     std::vector<std::vector<void *>> P;
     bool staged = false;
     Program pr;
@@ -483,6 +490,8 @@ int reduce_scatter_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, const in
         pr.is_fold = true;
         pr.order = {0};
         pr.nr = 1;
+    } else if (nbc) {
+        if (!nbc_program(2, c->size, NBC_BINOMIAL, 0, &pr)) return set_error(MI355X_ERR_UNSUPPORTED, "schedule too large");
     } else if (alg == RS_RING) {
         pr = reduce_scatter_ring_block_program(c->size, c->rank);
     } else if (alg == RS_NONOVERLAPPING) {
@@ -498,7 +507,7 @@ int reduce_scatter_impl(mi355x_comm_t *c, const void *sbuf, void *rbuf, const in
     }
     size_t max_block = 0;
     for (int r = 0; r < c->size; ++r) max_block = std::max(max_block, (size_t)rcounts[r]);
-    const bool pull_cand = !inplace && svc_rs_usable(c, max_block * esz, pr);  // the resident service evaluates
+    const bool pull_cand = !nbc && !inplace && svc_rs_usable(c, max_block * esz, pr);  // the resident service evaluates
     c->svc_keep = pull_cand;
     rc = exchange(c, 1, mine, sig, P, &staged);
     c->svc_keep = false;
@@ -768,6 +777,34 @@ int mi355x_ireduce_scatter_block(mi355x_comm_t *c, const void *sbuf, void *rbuf,
     if (nbc && (rc = nbc_check(c, 2, rcount * (size_t)c->size, type, false, 0))) return rc;
     return post(c, stream,
                 [=](hipStream_t s) { return reduce_scatter_block_impl(c, sbuf, rbuf, rcount, type, op, s, nbc); }, req);
+}
+// (the counts are copied at the post: the caller's array is free as soon as this returns)
+int mi355x_ireduce_scatter(mi355x_comm_t *c, const void *sbuf, void *rbuf, const int *rcounts, int type, int op,
+                           void *stream, mi355x_request_t **req)
+{
+    int rc = check_common(c, op, type);
+    if (rc) return rc;
+    if (!rcounts) return set_error(MI355X_ERR_ARG, "rcounts is NULL");
+    if (!req) return set_error(MI355X_ERR_ARG, "request pointer is NULL");
+    std::vector<int> counts(rcounts, rcounts + c->size);
+    size_t count = 0;
+    for (int n : counts) {
+        if (n < 0) return set_error(MI355X_ERR_ARG, "negative rcount");
+        count += (size_t)n;
+    }
+    const bool nbc = c->nb_order != 0;
+    if (nbc && (rc = nbc_check(c, 3, count, type, false, 0))) return rc;
+    if (count == 0) {  // nothing to exchange on any rank: complete, no buffer touched
+        auto *r = new mi355x_request();
+        r->done.store(1, std::memory_order_release);
+        *req = r;
+        return MI355X_SUCCESS;
+    }
+    return post(c, stream,
+                [c, sbuf, rbuf, counts = std::move(counts), type, op, nbc](hipStream_t s) {
+                    return reduce_scatter_impl(c, sbuf, rbuf, counts.data(), type, op, s, nbc);
+                },
+                req);
 }
 int mi355x_iallgather(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, void *stream,
                       mi355x_request_t **req)

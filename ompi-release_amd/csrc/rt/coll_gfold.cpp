@@ -245,16 +245,18 @@ int gfold_reduce_scatter_block(mi355x_comm *c, const void *in, void *rbuf, size_
 }
 
 int gfold_reduce_scatter(mi355x_comm *c, const void *in, void *rbuf, const size_t *disp, int type, int op,
-                         hipStream_t s)
+                         hipStream_t s, bool nbc)
 {
     const size_t count = disp[c->size], esz = mi355x_type_size(type);
-    const int alg = pick_reduce_scatter(c, count, esz);
+    const int alg = nbc ? (int)NBC_BINOMIAL : pick_reduce_scatter(c, count, esz);
     c->last_alg = alg;
     GfSeg sg;
     if (c->size == 1) {
         sg.pr.is_fold = true;
         sg.pr.order = {0};
         sg.pr.nr = 1;
+    } else if (nbc) {  // coll/libnbc: binomial to rank 0 + scatter (nbc_ireduce_scatter.c:37-164)
+        if (!nbc_program(2, c->size, NBC_BINOMIAL, 0, &sg.pr)) return set_error(MI355X_ERR_UNSUPPORTED, "schedule too large");
     } else if (alg == RS_RING) {
         sg.pr = reduce_scatter_ring_block_program(c->size, c->rank);
     } else if (alg == RS_NONOVERLAPPING) {
@@ -268,7 +270,9 @@ int gfold_reduce_scatter(mi355x_comm *c, const void *in, void *rbuf, const size_
     sg.e0 = disp[c->rank];
     sg.ne = disp[c->rank + 1] - disp[c->rank];
     sg.dst = static_cast<char *>(rbuf);
-    return gather_fold(c, in, count, type, op, std::vector<GfSeg>(1, sg), s);
+    const int rc = gather_fold(c, in, count, type, op, std::vector<GfSeg>(1, sg), s);
+    if (nbc) c->last_alg = alg;  // (the gather's own allgather calls report theirs)
+    return rc;
 }
 
 int gfold_scan(mi355x_comm *c, const void *in, void *rbuf, size_t count, int type, int op, int last, hipStream_t s,

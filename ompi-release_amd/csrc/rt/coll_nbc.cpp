@@ -1,6 +1,6 @@
 // coll_nbc.cpp -- coll/libnbc's operand order for the nonblocking reductions.
 //
-// In the reference MPI_Iallreduce, MPI_Ireduce and MPI_Ireduce_scatter_block belong to coll/libnbc
+// In the reference MPI_Iallreduce, MPI_Ireduce and MPI_Ireduce_scatter(_block) belong to coll/libnbc
 // (coll/cuda fills no nonblocking slot): libnbc picks its own algorithms with its own thresholds
 // and applies every reduction step as a 3-buff call, target = in1 (op) in2, with the rank's own
 // data as in1 (NBC_Sched_op, nbc.c:123-145; ompi_3buff_op_reduce, nbc.c:446-467).  This file
@@ -224,14 +224,15 @@ using namespace mi355x;
 extern "C" {
 
 // host-only introspection (tests; no GPU): libnbc's selection for coll 0 = MPI_Iallreduce,
-// 1 = MPI_Ireduce, 2 = MPI_Ireduce_scatter_block of `bytes` bytes over n ranks
+// 1 = MPI_Ireduce, 2 = MPI_Ireduce_scatter_block, 3 = MPI_Ireduce_scatter of `bytes` bytes over n ranks
 int mi355x_nbc_decision(int coll, int n, size_t bytes, int inplace)
 {
     if (n < 1 || n > kMaxRanks) return set_error(MI355X_ERR_ARG, "bad communicator size");
     switch (coll) {
     case 0: return nbc_iallreduce_decision(n, bytes, 1, inplace != 0);
     case 1: return nbc_ireduce_decision(n, bytes, 1);
-    case 2: return NBC_BINOMIAL;
+    case 2:
+    case 3: return NBC_BINOMIAL;  // (nbc_ireduce_scatter.c:37-164 has one schedule)
     default: return set_error(MI355X_ERR_ARG, "unknown collective %d", coll);
     }
 }

@@ -91,7 +91,8 @@ int nbc_iallreduce_decision(int n, size_t count, size_t dsize, bool inplace);  /
 int nbc_ireduce_decision(int n, size_t count, size_t dsize);                   // nbc_ireduce.c:74-88
 // binomial tree to `root`, rank 0 and the root swapped (RANK2VRANK; nbc_ireduce.c:211-285); with
 // root 0 also MPI_Iallreduce's tree (allred_sched_diss, nbc_iallreduce.c:225-272) and
-// MPI_Ireduce_scatter_block's (coll_libnbc_ireduce_scatter_block.c:78-116)
+// MPI_Ireduce_scatter_block's (coll_libnbc_ireduce_scatter_block.c:78-116) and MPI_Ireduce_scatter's
+// (nbc_ireduce_scatter.c:84-137)
 int expr_nbc_binomial(ExprPool &p, int n, int root);
 int expr_nbc_reduce_chain(ExprPool &p, int n, int root);  // red_sched_chain, nbc_ireduce.c:288-340
 // ring (allred_sched_ring, nbc_iallreduce.c:304-471): segment e is folded x_{e-1}, x_e, ...,
@@ -101,7 +102,7 @@ Program nbc_ring_segment_program(int n, int e);
 // is short, those after it empty
 void nbc_ring_block(size_t count, int n, int e, size_t *off, size_t *len);
 // the program of `alg` (NbcAlg) for MPI_Iallreduce (coll 0; block = ring segment), MPI_Ireduce
-// (coll 1; block = root) or MPI_Ireduce_scatter_block (coll 2); false: it does not fit the device
+// (coll 1; block = root) or MPI_Ireduce_scatter(_block) (coll 2); false: it does not fit the device
 bool nbc_program(int coll, int n, int alg, int block, Program *out);
 
 } // namespace mi355x

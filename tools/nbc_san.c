@@ -89,7 +89,7 @@ int main(void)
                 CHECK(a >= 101 && a <= 103 && b == 101, "decision coll %d n %d: %d %d", coll, n, a, b);
             }
     }
-    CHECK(mi355x_nbc_decision(3, 4, 1, 0) == MI355X_ERR_ARG && mi355x_nbc_decision(0, 65, 1, 0) == MI355X_ERR_ARG, "bad arguments accepted");
+    CHECK(mi355x_nbc_decision(4, 4, 1, 0) == MI355X_ERR_ARG && mi355x_nbc_decision(0, 65, 1, 0) == MI355X_ERR_ARG, "bad arguments accepted");
     printf(fails ? "nbc_san: %d FAILED\n" : "nbc_san: OK\n", fails);
     return fails ? 1 : 0;
 }
