@@ -19,58 +19,26 @@ int mca_coll_mi355x_priority = 90;
 int mca_coll_mi355x_allreduce_algorithm = 0;
 int mca_coll_mi355x_pml_hook = 1;
 
+/* The collective slots the component takes, once: (name, optional).  The module's prev_<name> /
+ * prev_<name>_module pairs, their release, their snapshot at enable time and the function table
+ * handed to MPI are all generated from this list, so a slot cannot be in one and not in another.
+ * Optional: the nonblocking slots, whose previous owner (normally coll/libnbc) may be absent. */
+#define COLL_SLOTS(X)                                                                              \
+    X(allreduce, 0) X(reduce_scatter, 0) X(reduce_scatter_block, 0) X(allgather, 0) X(bcast, 0)   \
+    X(reduce, 0) X(gather, 0) X(gatherv, 0) X(scatter, 0) X(scatterv, 0) X(allgatherv, 0)         \
+    X(alltoall, 0) X(alltoallv, 0) X(scan, 0) X(exscan, 0)                                         \
+    X(iallreduce, 1) X(ireduce, 1) X(ireduce_scatter_block, 1) X(ireduce_scatter, 1)               \
+    X(iallgather, 1) X(ibcast, 1) X(iscan, 1) X(iexscan, 1)
+
 typedef struct mca_coll_mi355x_module_t {
     mca_coll_base_module_t super;
     mi355x_comm_t *engine;
     /* lower-priority functions snapshotted at enable time (coll_cuda_module.c:126-147) */
-    mca_coll_base_module_allreduce_fn_t prev_allreduce;
-    mca_coll_base_module_t *prev_allreduce_module;
-    mca_coll_base_module_reduce_scatter_fn_t prev_reduce_scatter;
-    mca_coll_base_module_t *prev_reduce_scatter_module;
-    mca_coll_base_module_reduce_scatter_block_fn_t prev_reduce_scatter_block;
-    mca_coll_base_module_t *prev_reduce_scatter_block_module;
-    mca_coll_base_module_allgather_fn_t prev_allgather;
-    mca_coll_base_module_t *prev_allgather_module;
-    mca_coll_base_module_bcast_fn_t prev_bcast;
-    mca_coll_base_module_t *prev_bcast_module;
-    mca_coll_base_module_reduce_fn_t prev_reduce;
-    mca_coll_base_module_t *prev_reduce_module;
-    /* the callers either side of the reduction path (coll_move.cpp) */
-    mca_coll_base_module_gather_fn_t prev_gather;
-    mca_coll_base_module_t *prev_gather_module;
-    mca_coll_base_module_gatherv_fn_t prev_gatherv;
-    mca_coll_base_module_t *prev_gatherv_module;
-    mca_coll_base_module_scatter_fn_t prev_scatter;
-    mca_coll_base_module_t *prev_scatter_module;
-    mca_coll_base_module_scatterv_fn_t prev_scatterv;
-    mca_coll_base_module_t *prev_scatterv_module;
-    mca_coll_base_module_allgatherv_fn_t prev_allgatherv;
-    mca_coll_base_module_t *prev_allgatherv_module;
-    mca_coll_base_module_alltoall_fn_t prev_alltoall;
-    mca_coll_base_module_t *prev_alltoall_module;
-    mca_coll_base_module_alltoallv_fn_t prev_alltoallv;
-    mca_coll_base_module_t *prev_alltoallv_module;
-    mca_coll_base_module_scan_fn_t prev_scan;
-    mca_coll_base_module_t *prev_scan_module;
-    mca_coll_base_module_exscan_fn_t prev_exscan;
-    mca_coll_base_module_t *prev_exscan_module;
-    /* nonblocking slots: the previous owner (normally coll/libnbc) may be absent */
-    mca_coll_base_module_iallreduce_fn_t prev_iallreduce;
-    mca_coll_base_module_t *prev_iallreduce_module;
-    mca_coll_base_module_iscan_fn_t prev_iscan;
-    mca_coll_base_module_t *prev_iscan_module;
-    mca_coll_base_module_iexscan_fn_t prev_iexscan;
-    mca_coll_base_module_t *prev_iexscan_module;
-    mca_coll_base_module_ireduce_fn_t prev_ireduce;
-    mca_coll_base_module_t *prev_ireduce_module;
-    mca_coll_base_module_ireduce_scatter_block_fn_t prev_ireduce_scatter_block;
-    mca_coll_base_module_t *prev_ireduce_scatter_block_module;
-    mca_coll_base_module_ireduce_scatter_fn_t prev_ireduce_scatter;
-    mca_coll_base_module_t *prev_ireduce_scatter_module;
-    mca_coll_base_module_iallgather_fn_t prev_iallgather;
-    mca_coll_base_module_t *prev_iallgather_module;
-    mca_coll_base_module_ibcast_fn_t prev_ibcast;
-    mca_coll_base_module_t *prev_ibcast_module;
+#define PREV_FIELDS(FN, OPTIONAL)                      \
+    mca_coll_base_module_##FN##_fn_t prev_##FN;        \
+    mca_coll_base_module_t *prev_##FN##_module;
+    COLL_SLOTS(PREV_FIELDS)
+#undef PREV_FIELDS
     /* GPU-convertor layouts of the derived datatypes seen on this communicator, and the packed
      * staging buffer (device memory; registered once, re-registered when it grows) */
     struct ddt_slot { uint64_t sig; const void *dt; mi355x_ddt_t *d; } ddt_cache[8];
@@ -95,29 +63,9 @@ static void release_prev(mca_coll_base_module_t *p)
 static void module_destruct(opal_object_t *o)
 {
     mca_coll_mi355x_module_t *m = (mca_coll_mi355x_module_t *)o;
-    release_prev(m->prev_allreduce_module);
-    release_prev(m->prev_reduce_scatter_module);
-    release_prev(m->prev_reduce_scatter_block_module);
-    release_prev(m->prev_allgather_module);
-    release_prev(m->prev_bcast_module);
-    release_prev(m->prev_reduce_module);
-    release_prev(m->prev_gather_module);
-    release_prev(m->prev_gatherv_module);
-    release_prev(m->prev_scatter_module);
-    release_prev(m->prev_scatterv_module);
-    release_prev(m->prev_allgatherv_module);
-    release_prev(m->prev_alltoall_module);
-    release_prev(m->prev_alltoallv_module);
-    release_prev(m->prev_scan_module);
-    release_prev(m->prev_exscan_module);
-    release_prev(m->prev_iallreduce_module);
-    release_prev(m->prev_iscan_module);
-    release_prev(m->prev_iexscan_module);
-    release_prev(m->prev_ireduce_module);
-    release_prev(m->prev_ireduce_scatter_block_module);
-    release_prev(m->prev_ireduce_scatter_module);
-    release_prev(m->prev_iallgather_module);
-    release_prev(m->prev_ibcast_module);
+#define RELEASE_PREV(FN, OPTIONAL) release_prev(m->prev_##FN##_module);
+    COLL_SLOTS(RELEASE_PREV)
+#undef RELEASE_PREV
     for (int i = 0; i < 8; ++i)
         if (m->ddt_cache[i].d) mi355x_ddt_destroy(m->ddt_cache[i].d);
     for (int i = 0; i < 2; ++i)
@@ -478,59 +426,6 @@ static int engine_op(const struct ompi_op_t *op, int t)
     return (op->o_flags & OMPI_OP_FLAGS_INTRINSIC) && t >= 0 && mi355x_comm_op_supported(op->o_f_to_c_index, t);
 }
 
-static int staged_allreduce(mca_coll_mi355x_module_t *m, void *sbuf, void *rbuf, int count,
-                            struct ompi_datatype_t *dtype, struct ompi_op_t *op, struct ompi_communicator_t *comm)
-{
-    const size_t span = dt_span(dtype, (size_t)count);
-    hstage_t st[2];
-    const int rc = hstage2(st, &sbuf, span, &rbuf, span, sbuf == MPI_IN_PLACE, span, dtype);
-    if (rc != OMPI_SUCCESS) return rc;
-    return hunstage2(st, m->prev_allreduce(sbuf, rbuf, count, dtype, op, comm, m->prev_allreduce_module));
-}
-
-/* coll_cuda_reduce.c:43-78; only the root's rbuf is significant */
-static int staged_reduce(mca_coll_mi355x_module_t *m, void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype,
-                         struct ompi_op_t *op, int root, struct ompi_communicator_t *comm)
-{
-    const int me = mi355x_comm_rank_of(comm), inplace = (sbuf == MPI_IN_PLACE);
-    const size_t span = dt_span(dtype, (size_t)count);
-    hstage_t st[2];
-    void *ra = me == root ? rbuf : NULL;
-    const int rc = hstage2(st, &sbuf, span, &ra, span, inplace, span, dtype);
-    if (rc != OMPI_SUCCESS) return rc;
-    return hunstage2(st, m->prev_reduce(sbuf, me == root ? ra : rbuf, count, dtype, op, root, comm, m->prev_reduce_module));
-}
-
-/* coll_cuda_reduce_scatter_block.c:45-83 (in place: rbuf holds the n blocks) */
-static int staged_reduce_scatter_block(mca_coll_mi355x_module_t *m, void *sbuf, void *rbuf, int rcount,
-                                       struct ompi_datatype_t *dtype, struct ompi_op_t *op,
-                                       struct ompi_communicator_t *comm)
-{
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    const size_t in = dt_span(dtype, (size_t)rcount * (size_t)mi355x_comm_size_of(comm));
-    const size_t out = dt_span(dtype, (size_t)rcount);
-    hstage_t st[2];
-    const int rc = hstage2(st, &sbuf, in, &rbuf, inplace ? in : out, inplace, out, dtype);
-    if (rc != OMPI_SUCCESS) return rc;
-    return hunstage2(st, m->prev_reduce_scatter_block(sbuf, rbuf, rcount, dtype, op, comm,
-                                                      m->prev_reduce_scatter_block_module));
-}
-
-/* staged like reduce_scatter_block (in place: rbuf holds every block) */
-static int staged_reduce_scatter(mca_coll_mi355x_module_t *m, void *sbuf, void *rbuf, int *rcounts,
-                                 struct ompi_datatype_t *dtype, struct ompi_op_t *op, struct ompi_communicator_t *comm)
-{
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm);
-    size_t total = 0;
-    for (int q = 0; q < n; ++q) total += (size_t)(rcounts[q] > 0 ? rcounts[q] : 0);
-    const size_t in = dt_span(dtype, total), out = dt_span(dtype, (size_t)(rcounts[me] > 0 ? rcounts[me] : 0));
-    hstage_t st[2];
-    const int rc = hstage2(st, &sbuf, in, &rbuf, inplace ? in : out, inplace, out, dtype);
-    if (rc != OMPI_SUCCESS) return rc;
-    return hunstage2(st, m->prev_reduce_scatter(sbuf, rbuf, rcounts, dtype, op, comm, m->prev_reduce_scatter_module));
-}
-
 /* the send and receive sides of a data-movement call staged to the host (coll/cuda's rule applied
  * to the movement collectives): the send span copied in; the receive span copied in too (its gaps
  * keep their bytes) and back after the call.  A side is (buffer, type, span); NULL / MPI_IN_PLACE /
@@ -565,101 +460,6 @@ static size_t vspan(const struct ompi_datatype_t *dt, int n, const int *counts, 
 }
 
 /* ------------------------------------------------------------------ collectives */
-int mca_coll_mi355x_allreduce(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype,
-                              struct ompi_op_t *op, struct ompi_communicator_t *comm,
-                              mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    const int t = reducible_type(dtype);
-    if (count < 0) return m->prev_allreduce(sbuf, rbuf, count, dtype, op, comm, m->prev_allreduce_module);
-    if (!engine_op(op, t)) return staged_allreduce(m, sbuf, rbuf, count, dtype, op, comm);
-    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
-    ROUTE_OR(m->prev_allreduce(sbuf, rbuf, count, dtype, op, comm, m->prev_allreduce_module),
-             staged_allreduce(m, sbuf, rbuf, count, dtype, op, comm));
-    if (dev) return map_rc(mi355x_allreduce(m->engine, inplace ? NULL : sbuf, rbuf, (size_t)count, t, op->o_f_to_c_index, NULL));
-    const size_t bytes = (size_t)count * mi355x_type_size(t);
-    int rc = MI355X_SUCCESS;
-    void *rd = inplace ? dev_in(m, 1, rbuf, bytes, &rc) : dev_out(m, 1, rbuf, bytes, &rc);
-    const void *sd = inplace ? NULL : dev_in(m, 0, sbuf, bytes, &rc);
-    if (rc == MI355X_SUCCESS) rc = mi355x_allreduce(m->engine, sd, rd, (size_t)count, t, op->o_f_to_c_index, NULL);
-    return map_rc(copy_back(rbuf, rd, bytes, rc));
-}
-
-/* MPI_Reduce: the root's rbuf and every rank's sbuf (MPI_IN_PLACE: the root's rbuf) on the device;
- * a non-root's rbuf is not significant and never looked at */
-int mca_coll_mi355x_reduce(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
-                           int root, struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int me = mi355x_comm_rank_of(comm);
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    const int t = reducible_type(dtype);
-    if ((inplace && me != root) || count < 0)
-        return m->prev_reduce(sbuf, rbuf, count, dtype, op, root, comm, m->prev_reduce_module);
-    if (!engine_op(op, t)) return staged_reduce(m, sbuf, rbuf, count, dtype, op, root, comm);
-    const int dev = (me != root || is_dev(rbuf)) && (inplace || is_dev(sbuf));
-    ROUTE_OR(m->prev_reduce(sbuf, rbuf, count, dtype, op, root, comm, m->prev_reduce_module),
-             staged_reduce(m, sbuf, rbuf, count, dtype, op, root, comm));
-    if (dev)
-        return map_rc(mi355x_reduce(m->engine, inplace ? NULL : sbuf, me == root ? rbuf : NULL, (size_t)count, t,
-                                    op->o_f_to_c_index, root, NULL));
-    const size_t bytes = (size_t)count * mi355x_type_size(t);
-    int rc = MI355X_SUCCESS;
-    void *rd = me != root ? NULL : inplace ? dev_in(m, 1, rbuf, bytes, &rc) : dev_out(m, 1, rbuf, bytes, &rc);
-    const void *sd = inplace ? NULL : dev_in(m, 0, sbuf, bytes, &rc);
-    if (rc == MI355X_SUCCESS) rc = mi355x_reduce(m->engine, sd, rd, (size_t)count, t, op->o_f_to_c_index, root, NULL);
-    return map_rc(me == root ? copy_back(rbuf, rd, bytes, rc) : rc);
-}
-
-int mca_coll_mi355x_reduce_scatter_block(void *sbuf, void *rbuf, int rcount, struct ompi_datatype_t *dtype,
-                                         struct ompi_op_t *op, struct ompi_communicator_t *comm,
-                                         mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    const int t = reducible_type(dtype);
-    if (rcount < 0)
-        return m->prev_reduce_scatter_block(sbuf, rbuf, rcount, dtype, op, comm, m->prev_reduce_scatter_block_module);
-    if (!engine_op(op, t)) return staged_reduce_scatter_block(m, sbuf, rbuf, rcount, dtype, op, comm);
-    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
-    ROUTE_OR(m->prev_reduce_scatter_block(sbuf, rbuf, rcount, dtype, op, comm, m->prev_reduce_scatter_block_module),
-             staged_reduce_scatter_block(m, sbuf, rbuf, rcount, dtype, op, comm));
-    if (dev)
-        return map_rc(mi355x_reduce_scatter_block(m->engine, inplace ? NULL : sbuf, rbuf, (size_t)rcount, t,
-                                                  op->o_f_to_c_index, NULL));
-    const size_t out = (size_t)rcount * mi355x_type_size(t), in = out * (size_t)mi355x_comm_size_of(comm);
-    int rc = MI355X_SUCCESS;
-    void *rd = inplace ? dev_in(m, 1, rbuf, in, &rc) : dev_out(m, 1, rbuf, out, &rc);
-    const void *sd = inplace ? NULL : dev_in(m, 0, sbuf, in, &rc);
-    if (rc == MI355X_SUCCESS)
-        rc = mi355x_reduce_scatter_block(m->engine, sd, rd, (size_t)rcount, t, op->o_f_to_c_index, NULL);
-    return map_rc(copy_back(rbuf, rd, out, rc));
-}
-
-int mca_coll_mi355x_reduce_scatter(void *sbuf, void *rbuf, int *rcounts, struct ompi_datatype_t *dtype,
-                                   struct ompi_op_t *op, struct ompi_communicator_t *comm,
-                                   mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    const int t = reducible_type(dtype);
-    const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm);
-    size_t total = 0;
-    for (int q = 0; q < n; ++q) total += (size_t)(rcounts[q] > 0 ? rcounts[q] : 0);
-    if (!engine_op(op, t)) return staged_reduce_scatter(m, sbuf, rbuf, rcounts, dtype, op, comm);
-    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
-    ROUTE_OR(m->prev_reduce_scatter(sbuf, rbuf, rcounts, dtype, op, comm, m->prev_reduce_scatter_module),
-             staged_reduce_scatter(m, sbuf, rbuf, rcounts, dtype, op, comm));
-    if (dev) return map_rc(mi355x_reduce_scatter(m->engine, inplace ? NULL : sbuf, rbuf, rcounts, t, op->o_f_to_c_index, NULL));
-    const size_t esz = mi355x_type_size(t), in = total * esz, out = (size_t)(rcounts[me] > 0 ? rcounts[me] : 0) * esz;
-    int rc = MI355X_SUCCESS;
-    void *rd = inplace ? dev_in(m, 1, rbuf, in, &rc) : dev_out(m, 1, rbuf, out, &rc);
-    const void *sd = inplace ? NULL : dev_in(m, 0, sbuf, in, &rc);
-    if (rc == MI355X_SUCCESS) rc = mi355x_reduce_scatter(m->engine, sd, rd, rcounts, t, op->o_f_to_c_index, NULL);
-    return map_rc(copy_back(rbuf, rd, out, rc));
-}
-
 static int staged_allgather(mca_coll_mi355x_module_t *m, void *sbuf, int scount, struct ompi_datatype_t *sdtype,
                             void *rbuf, int rcount, struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm)
 {
@@ -770,7 +570,7 @@ int mca_coll_mi355x_bcast(void *buff, int count, struct ompi_datatype_t *datatyp
     return map_rc(rc);
 }
 
-/* ------------------------------------------------------------------ gather / scatter / alltoall / scan
+/* ------------------------------------------------------------------ gather / scatter / alltoall
  * Which path a call takes may depend only on what MPI requires to agree across ranks (the type
  * SIGNATURES, so the byte counts, and the op) and on where the buffers are: never on a rank-local
  * datatype LAYOUT, which MPI lets differ between ranks (a root may receive into a resized column
@@ -1072,77 +872,32 @@ int mca_coll_mi355x_alltoallv(void *sbuf, int *scounts, int *sdisps, struct ompi
     return finish_unpack(m, &rcv, erc);
 }
 
-static int scan_common(mca_coll_mi355x_module_t *m, int exclusive, void *sbuf, void *rbuf, int count,
-                       struct ompi_datatype_t *dtype, struct ompi_op_t *op, struct ompi_communicator_t *comm)
-{
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    const int t = reducible_type(dtype);
-#define SCAN_PREV(S, R)                                                                              \
-    (exclusive ? m->prev_exscan(S, R, count, dtype, op, comm, m->prev_exscan_module)                 \
-               : m->prev_scan(S, R, count, dtype, op, comm, m->prev_scan_module))
-    if (count < 0) return SCAN_PREV(sbuf, rbuf);
-    /* coll_cuda_scan.c:41-76 / coll_cuda_exscan.c:41-76; rbuf is copied in for MPI_IN_PLACE and
-     * for exscan (rank 0's rbuf is left as it was) */
-#define SCAN_STAGED()                                                                                 \
-    ({                                                                                                \
-        const size_t span_ = dt_span(dtype, (size_t)count);                                          \
-        hstage_t st_[2];                                                                              \
-        void *s_ = sbuf, *r_ = rbuf;                                                                  \
-        const int rc_ = hstage2(st_, &s_, span_, &r_, span_, inplace || exclusive, span_, dtype);     \
-        rc_ != OMPI_SUCCESS ? rc_ : hunstage2(st_, SCAN_PREV(s_, r_));                                \
-    })
-    if (!engine_op(op, t)) return SCAN_STAGED();
-    /* every rank votes its buffer kind, as for allreduce: a rank with host buffers joins the engine
-     * on device copies when a peer has device buffers */
-    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
-    ROUTE_OR(SCAN_PREV(sbuf, rbuf), SCAN_STAGED());
-#undef SCAN_STAGED
-#undef SCAN_PREV
-    if (dev)
-        return map_rc((exclusive ? mi355x_exscan : mi355x_scan)(m->engine, inplace ? NULL : sbuf, rbuf, (size_t)count,
-                                                                t, op->o_f_to_c_index, NULL));
-    const size_t bytes = (size_t)count * mi355x_type_size(t);
-    int rc = MI355X_SUCCESS;
-    void *rd = (inplace || exclusive) ? dev_in(m, 1, rbuf, bytes, &rc) : dev_out(m, 1, rbuf, bytes, &rc);
-    const void *sd = inplace ? NULL : dev_in(m, 0, sbuf, bytes, &rc);
-    if (rc == MI355X_SUCCESS)
-        rc = (exclusive ? mi355x_exscan : mi355x_scan)(m->engine, sd, rd, (size_t)count, t, op->o_f_to_c_index, NULL);
-    return map_rc(copy_back(rbuf, rd, bytes, rc));
-}
-
-int mca_coll_mi355x_scan(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
-                         struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
-{
-    return scan_common(MOD(module), 0, sbuf, rbuf, count, dtype, op, comm);
-}
-
-int mca_coll_mi355x_exscan(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
-                           struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
-{
-    return scan_common(MOD(module), 1, sbuf, rbuf, count, dtype, op, comm);
-}
-
 /* ------------------------------------------------------------------ nonblocking collectives
  * The engine runs a posted collective on the communicator's progress thread (mi355x_i*); the
  * component hands MPI an ompi_request_t subclass -- as coll/libnbc does
  * (coll_libnbc_component.c:300-333, coll_libnbc.h:120-135) -- and completes it from an
  * opal_progress callback (libnbc: ompi_coll_libnbc_progress, :239-268) when the engine request
  * has finished.  MPI_Wait / MPI_Test then find it complete and call req_free. */
+/* derived datatypes (iallgather / ibcast) and host ranks joining the engine: the bytes travel
+ * through `stage` (device memory, owned by the request once it starts); at completion they are moved
+ * into (ubuf, ucount, ud) -- ud NULL: copied -- before MPI sees the request complete, then stage,
+ * ud and pd are released */
+struct nb_stage {
+    void *stage;
+    size_t bytes;
+    void *ubuf;       /* NULL: nothing to unpack on this rank */
+    size_t ucount;
+    mi355x_ddt_t *ud; /* owned by the request; NULL with ubuf set: a plain copy */
+    mi355x_ddt_t *pd; /* layout of the initiation-time pack, owned by the request (kept until completion) */
+    int uhost;        /* ubuf is host memory: copied (ud NULL) or host-unpacked (ud) */
+};
+
 typedef struct mi355x_nbreq_t {
     ompi_request_t super;
     mi355x_request_t *eng;
     int p2p;                       /* 0 collective, 1 send, 2 receive (status filled at completion) */
     struct mi355x_nbreq_t *next;   /* active list */
-    /* derived datatypes (iallgather / ibcast): the packed bytes travel through `stage` (owned by
-     * the request); at completion they are unpacked into (ubuf, ucount, ud) -- ud NULL: copied --
-     * before MPI sees the request complete, then stage and ud are released */
-    void *stage;
-    size_t stage_bytes;
-    void *ubuf;
-    size_t ucount;
-    mi355x_ddt_t *ud;
-    mi355x_ddt_t *pd;              /* layout of the initiation-time pack (kept until completion) */
-    int uhost;                     /* ubuf is host memory: copied (ud NULL) or host-unpacked (ud) */
+    struct nb_stage st;
     /* persistent point-to-point (pml_isend_init / pml_irecv_init): 1 send, 2 receive, 0 none; the
      * arguments each MPI_Start posts */
     int pers;
@@ -1203,46 +958,31 @@ static void nbreq_construct(opal_object_t *o)
     r->super.req_status._cancelled = 0;
     r->super.req_free = nbreq_free;
     r->super.req_cancel = nbreq_cancel;
-    r->eng = NULL;
-    r->next = NULL;
-    r->stage = NULL;
-    r->stage_bytes = 0;
-    r->ubuf = NULL;
-    r->ucount = 0;
-    r->ud = NULL;
-    r->pd = NULL;
-    r->uhost = 0;
-    r->pers = 0;
-    r->pbuf = NULL;
-    r->pcount = 0;
-    r->pdt = NULL;
-    r->ppeer = r->ptag = r->pmode = 0;
-    r->free_called = 0;
-    r->inner = NULL;
-    memset(r->hs, 0, sizeof(r->hs));
+    memset((char *)r + sizeof(r->super), 0, sizeof(*r) - sizeof(r->super));
 }
 
 /* completion-time unpack of a derived-datatype nonblocking collective (local work only) */
 static int nb_finish_stage(mi355x_nbreq_t *r, int rc)
 {
-    if (!r->stage) return rc;
-    if (rc == MI355X_SUCCESS && r->ubuf && r->uhost && r->ud) {  /* host layout: host convertor */
-        void *tmp = malloc(r->stage_bytes ? r->stage_bytes : 1);
-        rc = tmp ? mi355x_memcpy(tmp, r->stage, r->stage_bytes) : MI355X_ERR_NOMEM;
-        if (rc == MI355X_SUCCESS) rc = mi355x_unpack_host(r->ud, r->ucount, r->ubuf, 0, tmp, r->stage_bytes);
+    struct nb_stage *st = &r->st;
+    if (!st->stage) return rc;
+    if (rc == MI355X_SUCCESS && st->ubuf && st->uhost && st->ud) {  /* host layout: host convertor */
+        void *tmp = malloc(st->bytes ? st->bytes : 1);
+        rc = tmp ? mi355x_memcpy(tmp, st->stage, st->bytes) : MI355X_ERR_NOMEM;
+        if (rc == MI355X_SUCCESS) rc = mi355x_unpack_host(st->ud, st->ucount, st->ubuf, 0, tmp, st->bytes);
         free(tmp);
-    } else if (rc == MI355X_SUCCESS && r->ubuf) {
-        rc = r->ud ? mi355x_unpack(r->ud, r->ucount, r->ubuf, 0, r->stage, r->stage_bytes, NULL, NULL)
-                   : mi355x_memcpy_async(r->ubuf, r->stage, r->stage_bytes, NULL);
+    } else if (rc == MI355X_SUCCESS && st->ubuf) {
+        rc = st->ud ? mi355x_unpack(st->ud, st->ucount, st->ubuf, 0, st->stage, st->bytes, NULL, NULL)
+                    : mi355x_memcpy_async(st->ubuf, st->stage, st->bytes, NULL);
         if (rc == MI355X_SUCCESS) rc = mi355x_stream_sync(NULL);
     } else {
         (void)mi355x_stream_sync(NULL);
     }
-    mi355x_free(r->stage);
-    r->stage = NULL;
-    if (r->ud) mi355x_ddt_destroy(r->ud);
-    if (r->pd) mi355x_ddt_destroy(r->pd);
-    r->ud = r->pd = NULL;
+    mi355x_free(st->stage);
+    st->stage = NULL;
+    if (st->ud) mi355x_ddt_destroy(st->ud);
+    if (st->pd) mi355x_ddt_destroy(st->pd);
+    st->ud = st->pd = NULL;
     return rc;
 }
 
@@ -1311,19 +1051,7 @@ static int nb_progress(void)
     return completed;
 }
 
-/* wrap an engine request into an active MPI request (OMPI_REQUEST_INIT + ACTIVE, coll_libnbc.h:
- * 126-131) */
-struct nb_stage {
-    void *stage;
-    size_t bytes;
-    void *ubuf;       /* NULL: nothing to unpack on this rank */
-    size_t ucount;
-    mi355x_ddt_t *ud; /* owned by the request; NULL with ubuf set: a plain copy */
-    mi355x_ddt_t *pd; /* layout of the initiation-time pack, owned by the request */
-    int uhost;        /* ubuf is host memory (the host convertor unpacks a derived layout) */
-};
-
-static void nb_stage_release(struct nb_stage *st)
+static void nb_stage_release(const struct nb_stage *st)
 {
     if (!st) return;
     (void)mi355x_stream_sync(NULL);
@@ -1345,8 +1073,23 @@ static void nb_activate(mi355x_nbreq_t *r)
     pthread_mutex_unlock(&nb_lock);
 }
 
-static int nb_start_full(mi355x_request_t *eng, struct ompi_communicator_t *comm, ompi_request_t **request, int p2p,
-                         struct nb_stage *st)
+/* hand MPI the new request r, active (OMPI_REQUEST_INIT + ACTIVE, coll_libnbc.h:126-131) */
+static int nb_launch(mi355x_nbreq_t *r, struct ompi_communicator_t *comm, ompi_request_t **request)
+{
+    r->super.req_complete = false;
+    r->super.req_persistent = false;
+    r->super.req_state = OMPI_REQUEST_ACTIVE;
+    r->super.req_status.MPI_ERROR = 0;
+    r->super.req_mpi_object.comm = comm;
+    nb_activate(r);
+    *request = &r->super;
+    return OMPI_SUCCESS;
+}
+
+/* wrap an engine request into an active MPI request.  p2p: 0 collective, 1 send, 2 receive; st: the
+ * staging the request takes over (NULL: none) */
+static int nb_start(mi355x_request_t *eng, struct ompi_communicator_t *comm, ompi_request_t **request, int p2p,
+                    const struct nb_stage *st)
 {
     mi355x_nbreq_t *r = (mi355x_nbreq_t *)mi355x_obj_new(&mi355x_nbreq_t_class);
     if (!r) {
@@ -1356,35 +1099,10 @@ static int nb_start_full(mi355x_request_t *eng, struct ompi_communicator_t *comm
         return OMPI_ERR_OUT_OF_RESOURCE;
     }
     r->p2p = p2p;
-    if (st) {
-        r->stage = st->stage;
-        r->stage_bytes = st->bytes;
-        r->ubuf = st->ubuf;
-        r->ucount = st->ucount;
-        r->ud = st->ud;
-        r->pd = st->pd;
-        r->uhost = st->uhost;
-    }
+    if (st) r->st = *st;
     if (p2p) r->super.req_type = OMPI_REQUEST_PML;
-    r->super.req_complete = false;
-    r->super.req_persistent = false;
-    r->super.req_state = OMPI_REQUEST_ACTIVE;
-    r->super.req_status.MPI_ERROR = 0;
-    r->super.req_mpi_object.comm = comm;
     r->eng = eng;
-    nb_activate(r);
-    *request = &r->super;
-    return OMPI_SUCCESS;
-}
-
-static int nb_start_kind(mi355x_request_t *eng, struct ompi_communicator_t *comm, ompi_request_t **request, int p2p)
-{
-    return nb_start_full(eng, comm, request, p2p, NULL);
-}
-
-static int nb_start(mi355x_request_t *eng, struct ompi_communicator_t *comm, ompi_request_t **request)
-{
-    return nb_start_kind(eng, comm, request, 0);
+    return nb_launch(r, comm, request);
 }
 
 #define NB_FALLBACK(FN, ...)                                                          \
@@ -1413,14 +1131,149 @@ static int nb_staged_start(struct ompi_communicator_t *comm, ompi_request_t **re
     r->inner = inner;
     r->hs[0] = st[0];
     r->hs[1] = st[1];
-    r->super.req_complete = false;
-    r->super.req_persistent = false;
-    r->super.req_state = OMPI_REQUEST_ACTIVE;
-    r->super.req_status.MPI_ERROR = 0;
-    r->super.req_mpi_object.comm = comm;
-    nb_activate(r);
-    *request = &r->super;
-    return OMPI_SUCCESS;
+    return nb_launch(r, comm, request);
+}
+
+/* ------------------------------------------------------------------ reductions
+ * allreduce, reduce, reduce_scatter_block, reduce_scatter, scan and exscan, blocking and nonblocking:
+ * each entry point validates its arguments, describes the call and hands the description to one of
+ * two drivers, which hold the decision ladder once:
+ *   1. a bad argument goes to the previous owner as it is;
+ *   2. an op or type the engine declines is staged through host memory to the previous owner;
+ *   3. the route: the buffer-kind vote (blocking), the mixed switch (nonblocking);
+ *   4. a rank with host buffers joins the engine on device copies of them;
+ *   5. a libnbc-ordered post the device cannot hold falls back to the staged path. */
+enum red_kind { RED_ALLREDUCE, RED_REDUCE, RED_REDUCE_SCATTER_BLOCK, RED_REDUCE_SCATTER, RED_SCAN };
+
+typedef struct {
+    enum red_kind kind;
+    int exclusive;   /* RED_SCAN: the exscan */
+    int root;        /* RED_REDUCE */
+    int bad;         /* an argument the engine does not take: the previous owner's to answer */
+    int no_prev;     /* a nonblocking slot nobody held before: no previous owner to go to */
+    void *sbuf, *rbuf;
+    int inplace;     /* sbuf == MPI_IN_PLACE */
+    int rsig;        /* rbuf is significant on this rank (reduce: on the root only).  Where it is not, it
+                        is never looked at, staged or copied back, and the engine gets NULL; a staged call
+                        hands the previous owner the caller's pointer when blocking and NULL when
+                        nonblocking (reduction_staged) */
+    int rfill;       /* the receive copy starts from rbuf's contents: in place, and every exscan (rank
+                        0's rbuf is left as it was) */
+    size_t in, out;  /* elements read (in place: from rbuf) and written: count / count, n x rcount /
+                        rcount, sum(rcounts) / rcounts[me] */
+    struct ompi_datatype_t *dtype;
+    struct ompi_op_t *op;
+    int t;           /* the engine's slot of dtype, < 0: none */
+    int count;       /* the caller's count or rcount */
+    int *rcounts;    /* ... or its recvcounts (RED_REDUCE_SCATTER) */
+} reduction_t;
+
+/* the engine's call on device memory (sd NULL: in place); eng NULL: blocking, else the post */
+static int red_engine(mca_coll_mi355x_module_t *m, const reduction_t *d, const void *sd, void *rd, mi355x_request_t **eng)
+{
+    mi355x_comm_t *e = m->engine;
+    const int t = d->t, op = d->op->o_f_to_c_index;
+    switch (d->kind) {
+    case RED_ALLREDUCE:
+        return eng ? mi355x_iallreduce(e, sd, rd, d->out, t, op, NULL, eng) : mi355x_allreduce(e, sd, rd, d->out, t, op, NULL);
+    case RED_REDUCE:
+        return eng ? mi355x_ireduce(e, sd, rd, d->out, t, op, d->root, NULL, eng)
+                   : mi355x_reduce(e, sd, rd, d->out, t, op, d->root, NULL);
+    case RED_REDUCE_SCATTER_BLOCK:
+        return eng ? mi355x_ireduce_scatter_block(e, sd, rd, d->out, t, op, NULL, eng)
+                   : mi355x_reduce_scatter_block(e, sd, rd, d->out, t, op, NULL);
+    case RED_REDUCE_SCATTER:  /* (the engine copies rcounts at the post) */
+        return eng ? mi355x_ireduce_scatter(e, sd, rd, d->rcounts, t, op, NULL, eng)
+                   : mi355x_reduce_scatter(e, sd, rd, d->rcounts, t, op, NULL);
+    default:
+        if (eng) return (d->exclusive ? mi355x_iexscan : mi355x_iscan)(e, sd, rd, d->out, t, op, NULL, eng);
+        return (d->exclusive ? mi355x_exscan : mi355x_scan)(e, sd, rd, d->out, t, op, NULL);
+    }
+}
+
+/* the previous owner's call on (s, r); request NULL: blocking, else the post */
+static int red_prev(mca_coll_mi355x_module_t *m, const reduction_t *d, void *s, void *r, struct ompi_communicator_t *comm,
+                    ompi_request_t **request)
+{
+    struct ompi_datatype_t *dt = d->dtype;
+    struct ompi_op_t *op = d->op;
+    switch (d->kind) {
+    case RED_ALLREDUCE:
+        return request ? m->prev_iallreduce(s, r, d->count, dt, op, comm, request, m->prev_iallreduce_module)
+                       : m->prev_allreduce(s, r, d->count, dt, op, comm, m->prev_allreduce_module);
+    case RED_REDUCE:
+        return request ? m->prev_ireduce(s, r, d->count, dt, op, d->root, comm, request, m->prev_ireduce_module)
+                       : m->prev_reduce(s, r, d->count, dt, op, d->root, comm, m->prev_reduce_module);
+    case RED_REDUCE_SCATTER_BLOCK:
+        return request ? m->prev_ireduce_scatter_block(s, r, d->count, dt, op, comm, request,
+                                                       m->prev_ireduce_scatter_block_module)
+                       : m->prev_reduce_scatter_block(s, r, d->count, dt, op, comm, m->prev_reduce_scatter_block_module);
+    case RED_REDUCE_SCATTER:
+        return request ? m->prev_ireduce_scatter(s, r, d->rcounts, dt, op, comm, request, m->prev_ireduce_scatter_module)
+                       : m->prev_reduce_scatter(s, r, d->rcounts, dt, op, comm, m->prev_reduce_scatter_module);
+    default:
+        if (d->exclusive)
+            return request ? m->prev_iexscan(s, r, d->count, dt, op, comm, request, m->prev_iexscan_module)
+                           : m->prev_exscan(s, r, d->count, dt, op, comm, m->prev_exscan_module);
+        return request ? m->prev_iscan(s, r, d->count, dt, op, comm, request, m->prev_iscan_module)
+                       : m->prev_scan(s, r, d->count, dt, op, comm, m->prev_scan_module);
+    }
+}
+
+/* the previous owner on the caller's own buffers (a bad argument; host buffers on every rank) */
+static int reduction_prev(mca_coll_mi355x_module_t *m, const reduction_t *d, struct ompi_communicator_t *comm,
+                          ompi_request_t **request)
+{
+    if (d->no_prev) return OMPI_ERR_NOT_SUPPORTED;
+    return red_prev(m, d, d->sbuf, d->rbuf, comm, request);
+}
+
+/* this rank's buffers are all device memory */
+static int red_dev(const reduction_t *d)
+{
+    return (!d->rsig || is_dev(d->rbuf)) && (d->inplace || is_dev(d->sbuf));
+}
+
+/* The previous owner with this rank's device buffers staged through host memory (coll/cuda's staging,
+ * above: coll_cuda_allreduce.c:43-75, coll_cuda_reduce.c:43-78, coll_cuda_reduce_scatter_block.c:
+ * 45-83, coll_cuda_scan.c:41-76, coll_cuda_exscan.c:41-76).  The send side spans the input and is
+ * never copied back; the receive side spans the input when in place (rbuf then holds every block),
+ * else the output, and the output is copied back.  A nonblocking form stages at initiation and copies
+ * back when the host request completes (nb_staged_start). */
+static int reduction_staged(mca_coll_mi355x_module_t *m, const reduction_t *d, struct ompi_communicator_t *comm,
+                            ompi_request_t **request)
+{
+    if (d->no_prev) return OMPI_ERR_NOT_SUPPORTED;
+    const size_t in = dt_span(d->dtype, d->in), out = dt_span(d->dtype, d->out);
+    hstage_t st[2];
+    void *s = d->sbuf, *r = d->rsig ? d->rbuf : NULL;
+    int rc = hstage2(st, &s, in, &r, d->inplace ? in : out, d->rfill, out, d->dtype);
+    if (rc != OMPI_SUCCESS) return rc;
+    if (!request) return hunstage2(st, red_prev(m, d, s, d->rsig ? r : d->rbuf, comm, NULL));
+    ompi_request_t *inner = NULL;
+    rc = red_prev(m, d, s, r, comm, &inner);
+    return nb_staged_start(comm, request, st, inner, rc);
+}
+
+/* Every rank votes its buffer kind (route): a call whose ranks all hold host buffers runs in the
+ * previous owner, a device rank of it staged; otherwise it runs in the engine, and a rank with host
+ * buffers joins on device copies in the module's scratch slots (0: send side, 1: receive side).  The
+ * vote is collective: it is taken only once the op is known to be the engine's, once per call. */
+static int reduction_blocking(mca_coll_mi355x_module_t *m, const reduction_t *d, struct ompi_communicator_t *comm)
+{
+    if (d->bad) return reduction_prev(m, d, comm, NULL);
+    if (!engine_op(d->op, d->t)) return reduction_staged(m, d, comm, NULL);
+    const int dev = red_dev(d);
+    const int engine = route(m, dev);
+    if (engine < 0) return OMPI_ERROR;
+    if (engine == 0) return dev ? reduction_staged(m, d, comm, NULL) : reduction_prev(m, d, comm, NULL);
+    if (dev) return map_rc(red_engine(m, d, d->inplace ? NULL : d->sbuf, d->rsig ? d->rbuf : NULL, NULL));
+    const size_t esz = mi355x_type_size(d->t), in = d->in * esz, out = d->out * esz;
+    int rc = MI355X_SUCCESS;
+    void *rd = !d->rsig ? NULL : d->rfill ? dev_in(m, 1, d->rbuf, d->inplace ? in : out, &rc) : dev_out(m, 1, d->rbuf, out, &rc);
+    const void *sd = d->inplace ? NULL : dev_in(m, 0, d->sbuf, in, &rc);
+    if (rc == MI355X_SUCCESS) rc = red_engine(m, d, sd, rd, NULL);
+    return map_rc(d->rsig ? copy_back(d->rbuf, rd, out, rc) : rc);
 }
 
 /* A nonblocking initiation may not wait for its peers (a vote would: MPI lets a rank start the
@@ -1429,30 +1282,32 @@ static int nb_staged_start(struct ompi_communicator_t *comm, ompi_request_t **re
  * rank enters the engine, and a rank whose buffers are host memory joins on device copies made at
  * initiation (its input) and copied back at completion (its output).  With
  * coll_mi355x_mixed_buffers = 0 every rank must use one kind, and host buffers go to the
- * lower-priority component as before. */
-static int nb_host_join(mca_coll_mi355x_module_t *m, void *sbuf, void *rbuf, int inplace, size_t in_bytes,
-                        size_t out_bytes, int rsig, void **sd, void **rd, struct nb_stage *st)
+ * lower-priority component as before.
+ * The copies are one per-request allocation, handed to the request in *st: the receive side first
+ * (filled from rbuf when d->rfill), then the send side. */
+static int nb_host_join(const reduction_t *d, size_t in_bytes, size_t out_bytes, void **sd, void **rd, struct nb_stage *st)
 {
-    const int rh = rsig && !is_dev(rbuf), sh = !inplace && !is_dev(sbuf);
+    const int rh = d->rsig && !is_dev(d->rbuf), sh = !d->inplace && !is_dev(d->sbuf);
     memset(st, 0, sizeof(*st));
-    *sd = inplace ? NULL : sbuf;
-    *rd = rsig ? rbuf : NULL;
+    *sd = d->inplace ? NULL : d->sbuf;
+    *rd = d->rsig ? d->rbuf : NULL;
     /* (never 0: the engine takes sbuf == rbuf for MPI_IN_PLACE, and a rank that receives nothing -- a
      * zero count of MPI_Ireduce_scatter -- would alias its two copies and alone take the in-place flow) */
-    const size_t rspan = inplace ? in_bytes : (out_bytes ? out_bytes : 16);
+    const size_t rspan = d->inplace ? in_bytes : (out_bytes ? out_bytes : 16);
     const size_t a = (rh ? rspan : 0) + (sh ? in_bytes : 0);
     if (mi355x_malloc(&st->stage, a ? a : 1) != MI355X_SUCCESS) return MI355X_ERR_NOMEM;
     int rc = MI355X_SUCCESS;
     if (rh) {
+        const size_t fill = d->inplace ? in_bytes : d->rfill ? out_bytes : 0;
         *rd = st->stage;
         st->bytes = out_bytes;
-        st->ubuf = rbuf;
+        st->ubuf = d->rbuf;
         st->uhost = 1;
-        if (inplace && in_bytes) rc = mi355x_memcpy(st->stage, rbuf, in_bytes);
+        if (fill) rc = mi355x_memcpy(st->stage, d->rbuf, fill);
     }
     if (sh && rc == MI355X_SUCCESS) {
         *sd = (char *)st->stage + (rh ? rspan : 0);
-        if (in_bytes) rc = mi355x_memcpy(*sd, sbuf, in_bytes);
+        if (in_bytes) rc = mi355x_memcpy(*sd, d->sbuf, in_bytes);
     }
     if (rc != MI355X_SUCCESS) {
         mi355x_free(st->stage);
@@ -1461,221 +1316,198 @@ static int nb_host_join(mca_coll_mi355x_module_t *m, void *sbuf, void *rbuf, int
     return rc;
 }
 
-/* the declined / host-buffer form of a nonblocking reduction: device buffers staged to the host */
-#define NB_STAGED(FN, SSPAN, RSPAN, RFILL, RBACK, DT, ...)                                       \
-    do {                                                                                          \
-        if (!m->prev_##FN) return OMPI_ERR_NOT_SUPPORTED;                                         \
-        hstage_t st_[2];                                                                          \
-        int rc_ = hstage2(st_, &sbuf, (SSPAN), &rbuf, (RSPAN), (RFILL), (RBACK), (DT));           \
-        if (rc_ != OMPI_SUCCESS) return rc_;                                                      \
-        ompi_request_t *in_ = NULL;                                                               \
-        rc_ = m->prev_##FN(__VA_ARGS__, &in_, m->prev_##FN##_module);                             \
-        return nb_staged_start(comm, request, st_, in_, rc_);                                     \
-    } while (0)
-
 /* a libnbc-ordered post (coll_mi355x_nb_order = 1) whose program the device cannot hold: every rank
  * gets this answer (it depends on the sizes only) and takes the staged path to the lower-priority
  * component -- libnbc itself */
 #define NB_UNFIT(RC) ((RC) == MI355X_ERR_UNSUPPORTED && mca_coll_mi355x_nb_order != 0)
 
+static int reduction_nonblocking(mca_coll_mi355x_module_t *m, const reduction_t *d, struct ompi_communicator_t *comm,
+                                 ompi_request_t **request)
+{
+    if (d->bad) return reduction_prev(m, d, comm, request);
+    const int dev = red_dev(d);
+    if (!engine_op(d->op, d->t) || (!dev && !m->mixed)) return reduction_staged(m, d, comm, request);
+    mi355x_request_t *eng = NULL;
+    int rc;
+    if (dev) {
+        rc = red_engine(m, d, d->inplace ? NULL : d->sbuf, d->rsig ? d->rbuf : NULL, &eng);
+        if (rc == MI355X_SUCCESS) return nb_start(eng, comm, request, 0, NULL);
+    } else {  /* host buffers: join the engine on device copies (nb_host_join) */
+        const size_t esz = mi355x_type_size(d->t);
+        struct nb_stage st;
+        void *sd, *rd;
+        rc = nb_host_join(d, d->in * esz, d->out * esz, &sd, &rd, &st);
+        if (rc == MI355X_SUCCESS) rc = red_engine(m, d, sd, rd, &eng);
+        if (rc == MI355X_SUCCESS) return nb_start(eng, comm, request, 0, &st);
+        nb_stage_release(&st);
+    }
+    return NB_UNFIT(rc) ? reduction_staged(m, d, comm, request) : map_rc(rc);
+}
+
+/* what allreduce, the scans and (with root) reduce share: count elements in, count out */
+static reduction_t red_count(enum red_kind kind, void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype,
+                             struct ompi_op_t *op)
+{
+    const int inplace = (sbuf == MPI_IN_PLACE);
+    return (reduction_t){.kind = kind, .bad = count < 0, .sbuf = sbuf, .rbuf = rbuf, .inplace = inplace, .rsig = 1,
+                         .rfill = inplace, .in = (size_t)count, .out = (size_t)count, .dtype = dtype, .op = op,
+                         .t = reducible_type(dtype), .count = count};
+}
+
+int mca_coll_mi355x_allreduce(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype,
+                              struct ompi_op_t *op, struct ompi_communicator_t *comm,
+                              mca_coll_base_module_t *module)
+{
+    const reduction_t d = red_count(RED_ALLREDUCE, sbuf, rbuf, count, dtype, op);
+    return reduction_blocking(MOD(module), &d, comm);
+}
+
 int mca_coll_mi355x_iallreduce(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
                                struct ompi_communicator_t *comm, ompi_request_t **request,
                                mca_coll_base_module_t *module)
 {
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    const int t = reducible_type(dtype);
-    if (count < 0) NB_FALLBACK(iallreduce, sbuf, rbuf, count, dtype, op, comm, request);
-    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
-    if (!engine_op(op, t) || (!dev && !m->mixed)) {
-        const size_t span = dt_span(dtype, (size_t)count);
-        NB_STAGED(iallreduce, span, span, inplace, span, dtype, sbuf, rbuf, count, dtype, op, comm);
-    }
-    mi355x_request_t *eng = NULL;
-    if (!dev) {  /* host buffers: join the engine on device copies (nb_host_join) */
-        const size_t bytes = (size_t)count * mi355x_type_size(t);
-        struct nb_stage st;
-        void *sd, *rd;
-        int rc = nb_host_join(m, sbuf, rbuf, inplace, bytes, bytes, 1, &sd, &rd, &st);
-        if (rc == MI355X_SUCCESS) rc = mi355x_iallreduce(m->engine, sd, rd, (size_t)count, t, op->o_f_to_c_index, NULL, &eng);
-        if (rc == MI355X_SUCCESS) return nb_start_full(eng, comm, request, 0, &st);
-        nb_stage_release(&st);
-        if (!NB_UNFIT(rc)) return map_rc(rc);
-    } else {
-        int rc = mi355x_iallreduce(m->engine, inplace ? NULL : sbuf, rbuf, (size_t)count, t, op->o_f_to_c_index, NULL, &eng);
-        if (!NB_UNFIT(rc)) return rc ? map_rc(rc) : nb_start(eng, comm, request);
-    }
-    const size_t span = dt_span(dtype, (size_t)count);
-    NB_STAGED(iallreduce, span, span, inplace, span, dtype, sbuf, rbuf, count, dtype, op, comm);
+    reduction_t d = red_count(RED_ALLREDUCE, sbuf, rbuf, count, dtype, op);
+    d.no_prev = !MOD(module)->prev_iallreduce;
+    return reduction_nonblocking(MOD(module), &d, comm, request);
+}
+
+/* MPI_Reduce: the root's rbuf and every rank's sbuf (MPI_IN_PLACE: the root's rbuf) on the device;
+ * a non-root's rbuf is not significant and never looked at (coll_cuda_reduce.c:43-78) */
+static reduction_t red_rooted(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
+                              int root, struct ompi_communicator_t *comm)
+{
+    reduction_t d = red_count(RED_REDUCE, sbuf, rbuf, count, dtype, op);
+    d.root = root;
+    d.rsig = mi355x_comm_rank_of(comm) == root;
+    d.bad = d.bad || (d.inplace && !d.rsig);
+    return d;
+}
+
+int mca_coll_mi355x_reduce(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
+                           int root, struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    const reduction_t d = red_rooted(sbuf, rbuf, count, dtype, op, root, comm);
+    return reduction_blocking(MOD(module), &d, comm);
 }
 
 int mca_coll_mi355x_ireduce(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
                             int root, struct ompi_communicator_t *comm, ompi_request_t **request,
                             mca_coll_base_module_t *module)
 {
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int me = mi355x_comm_rank_of(comm);
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    const int t = reducible_type(dtype);
-    if (count < 0 || (inplace && me != root)) NB_FALLBACK(ireduce, sbuf, rbuf, count, dtype, op, root, comm, request);
-    const int dev = (me != root || is_dev(rbuf)) && (inplace || is_dev(sbuf));
-    if (!engine_op(op, t) || (!dev && !m->mixed)) {
-        const size_t span = dt_span(dtype, (size_t)count);
-        if (me != root) rbuf = NULL;  /* not significant off the root: never staged */
-        NB_STAGED(ireduce, span, span, inplace, span, dtype, sbuf, rbuf, count, dtype, op, root, comm);
-    }
-    mi355x_request_t *eng = NULL;
-    if (!dev) {  /* host buffers: join the engine on device copies (nb_host_join) */
-        const size_t bytes = (size_t)count * mi355x_type_size(t);
-        struct nb_stage st;
-        void *sd, *rd;
-        int rc = nb_host_join(m, sbuf, rbuf, inplace, bytes, bytes, me == root, &sd, &rd, &st);
-        if (rc == MI355X_SUCCESS)
-            rc = mi355x_ireduce(m->engine, sd, rd, (size_t)count, t, op->o_f_to_c_index, root, NULL, &eng);
-        if (rc == MI355X_SUCCESS) return nb_start_full(eng, comm, request, 0, &st);
-        nb_stage_release(&st);
-        if (!NB_UNFIT(rc)) return map_rc(rc);
-    } else {
-        int rc = mi355x_ireduce(m->engine, inplace ? NULL : sbuf, me == root ? rbuf : NULL, (size_t)count, t,
-                                op->o_f_to_c_index, root, NULL, &eng);
-        if (!NB_UNFIT(rc)) return rc ? map_rc(rc) : nb_start(eng, comm, request);
-    }
-    const size_t span = dt_span(dtype, (size_t)count);
-    if (me != root) rbuf = NULL;  /* not significant off the root: never staged */
-    NB_STAGED(ireduce, span, span, inplace, span, dtype, sbuf, rbuf, count, dtype, op, root, comm);
+    reduction_t d = red_rooted(sbuf, rbuf, count, dtype, op, root, comm);
+    d.no_prev = !MOD(module)->prev_ireduce;
+    return reduction_nonblocking(MOD(module), &d, comm, request);
+}
+
+/* coll_cuda_reduce_scatter_block.c:45-83 (in place: rbuf holds the n blocks) */
+static reduction_t red_block(void *sbuf, void *rbuf, int rcount, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
+                             struct ompi_communicator_t *comm)
+{
+    reduction_t d = red_count(RED_REDUCE_SCATTER_BLOCK, sbuf, rbuf, rcount, dtype, op);
+    d.in = (size_t)rcount * (size_t)mi355x_comm_size_of(comm);
+    return d;
+}
+
+int mca_coll_mi355x_reduce_scatter_block(void *sbuf, void *rbuf, int rcount, struct ompi_datatype_t *dtype,
+                                         struct ompi_op_t *op, struct ompi_communicator_t *comm,
+                                         mca_coll_base_module_t *module)
+{
+    const reduction_t d = red_block(sbuf, rbuf, rcount, dtype, op, comm);
+    return reduction_blocking(MOD(module), &d, comm);
 }
 
 int mca_coll_mi355x_ireduce_scatter_block(void *sbuf, void *rbuf, int rcount, struct ompi_datatype_t *dtype,
                                           struct ompi_op_t *op, struct ompi_communicator_t *comm,
                                           ompi_request_t **request, mca_coll_base_module_t *module)
 {
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    const int t = reducible_type(dtype);
-    if (rcount < 0) NB_FALLBACK(ireduce_scatter_block, sbuf, rbuf, rcount, dtype, op, comm, request);
-    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
-    if (!engine_op(op, t) || (!dev && !m->mixed)) {
-        const size_t in = dt_span(dtype, (size_t)rcount * (size_t)mi355x_comm_size_of(comm));
-        const size_t out = dt_span(dtype, (size_t)rcount);
-        NB_STAGED(ireduce_scatter_block, in, inplace ? in : out, inplace, out, dtype, sbuf, rbuf, rcount, dtype, op,
-                  comm);
-    }
-    mi355x_request_t *eng = NULL;
-    if (!dev) {  /* host buffers: join the engine on device copies (nb_host_join) */
-        const size_t out = (size_t)rcount * mi355x_type_size(t), in = out * (size_t)mi355x_comm_size_of(comm);
-        struct nb_stage st;
-        void *sd, *rd;
-        int rc = nb_host_join(m, sbuf, rbuf, inplace, in, out, 1, &sd, &rd, &st);
-        if (rc == MI355X_SUCCESS)
-            rc = mi355x_ireduce_scatter_block(m->engine, sd, rd, (size_t)rcount, t, op->o_f_to_c_index, NULL, &eng);
-        if (rc == MI355X_SUCCESS) return nb_start_full(eng, comm, request, 0, &st);
-        nb_stage_release(&st);
-        if (!NB_UNFIT(rc)) return map_rc(rc);
-    } else {
-        int rc = mi355x_ireduce_scatter_block(m->engine, inplace ? NULL : sbuf, rbuf, (size_t)rcount, t,
-                                              op->o_f_to_c_index, NULL, &eng);
-        if (!NB_UNFIT(rc)) return rc ? map_rc(rc) : nb_start(eng, comm, request);
-    }
-    const size_t in = dt_span(dtype, (size_t)rcount * (size_t)mi355x_comm_size_of(comm));
-    const size_t out = dt_span(dtype, (size_t)rcount);
-    NB_STAGED(ireduce_scatter_block, in, inplace ? in : out, inplace, out, dtype, sbuf, rbuf, rcount, dtype, op, comm);
+    reduction_t d = red_block(sbuf, rbuf, rcount, dtype, op, comm);
+    d.no_prev = !MOD(module)->prev_ireduce_scatter_block;
+    return reduction_nonblocking(MOD(module), &d, comm, request);
 }
 
-/* MPI_Ireduce_scatter (vector counts): in the reference coll/libnbc's, whose schedule receives into a
- * host tmpbuf and reduces it with sendbuf (nbc_ireduce_scatter.c:87-111) -- not usable on device
- * buffers.  Shaped like ireduce_scatter_block above: the input spans the whole vector, the output
- * this rank's count (0 for a rank that receives nothing); the engine copies rcounts at the post. */
+/* MPI_Reduce_scatter (vector counts), staged and joined like the block form: the input spans the whole
+ * vector (in place: rbuf holds every block), the output this rank's count -- 0 for a rank that receives
+ * nothing, which still takes part.  strict: a NULL or negative count is a bad argument (the nonblocking
+ * form, before anything is computed); else negative counts read as 0 (the blocking form, which has
+ * no bad-argument path). */
+static reduction_t red_vector(void *sbuf, void *rbuf, int *rcounts, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
+                              struct ompi_communicator_t *comm, int strict)
+{
+    reduction_t d = red_count(RED_REDUCE_SCATTER, sbuf, rbuf, 0, dtype, op);
+    const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm);
+    d.rcounts = rcounts;
+    for (int q = 0; q < n && !d.bad; ++q) {
+        if (strict && (!rcounts || rcounts[q] < 0)) d.bad = 1;
+        else d.in += (size_t)(rcounts[q] > 0 ? rcounts[q] : 0);
+    }
+    if (!d.bad) d.out = (size_t)(rcounts[me] > 0 ? rcounts[me] : 0);
+    return d;
+}
+
+int mca_coll_mi355x_reduce_scatter(void *sbuf, void *rbuf, int *rcounts, struct ompi_datatype_t *dtype,
+                                   struct ompi_op_t *op, struct ompi_communicator_t *comm,
+                                   mca_coll_base_module_t *module)
+{
+    const reduction_t d = red_vector(sbuf, rbuf, rcounts, dtype, op, comm, 0);
+    return reduction_blocking(MOD(module), &d, comm);
+}
+
+/* MPI_Ireduce_scatter: in the reference coll/libnbc's, whose schedule receives into a host tmpbuf and
+ * reduces it with sendbuf (nbc_ireduce_scatter.c:87-111) -- not usable on device buffers */
 int mca_coll_mi355x_ireduce_scatter(void *sbuf, void *rbuf, int *rcounts, struct ompi_datatype_t *dtype,
                                     struct ompi_op_t *op, struct ompi_communicator_t *comm, ompi_request_t **request,
                                     mca_coll_base_module_t *module)
 {
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    const int t = reducible_type(dtype);
-    const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm);
-    size_t total = 0;
-    for (int q = 0; q < n; ++q) {
-        if (!rcounts || rcounts[q] < 0) NB_FALLBACK(ireduce_scatter, sbuf, rbuf, rcounts, dtype, op, comm, request);
-        total += (size_t)rcounts[q];
-    }
-    const size_t in = dt_span(dtype, total), out = dt_span(dtype, (size_t)rcounts[me]);
-    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
-    if (!engine_op(op, t) || (!dev && !m->mixed))
-        NB_STAGED(ireduce_scatter, in, inplace ? in : out, inplace, out, dtype, sbuf, rbuf, rcounts, dtype, op, comm);
-    mi355x_request_t *eng = NULL;
-    if (!dev) {  /* host buffers: join the engine on device copies (nb_host_join) */
-        const size_t esz = mi355x_type_size(t);
-        struct nb_stage st;
-        void *sd, *rd;
-        int rc = nb_host_join(m, sbuf, rbuf, inplace, total * esz, (size_t)rcounts[me] * esz, 1, &sd, &rd, &st);
-        if (rc == MI355X_SUCCESS)
-            rc = mi355x_ireduce_scatter(m->engine, sd, rd, rcounts, t, op->o_f_to_c_index, NULL, &eng);
-        if (rc == MI355X_SUCCESS) return nb_start_full(eng, comm, request, 0, &st);
-        nb_stage_release(&st);
-        if (!NB_UNFIT(rc)) return map_rc(rc);
-    } else {
-        int rc = mi355x_ireduce_scatter(m->engine, inplace ? NULL : sbuf, rbuf, rcounts, t, op->o_f_to_c_index, NULL, &eng);
-        if (!NB_UNFIT(rc)) return rc ? map_rc(rc) : nb_start(eng, comm, request);
-    }
-    NB_STAGED(ireduce_scatter, in, inplace ? in : out, inplace, out, dtype, sbuf, rbuf, rcounts, dtype, op, comm);
+    reduction_t d = red_vector(sbuf, rbuf, rcounts, dtype, op, comm, 1);
+    d.no_prev = !MOD(module)->prev_ireduce_scatter;
+    return reduction_nonblocking(MOD(module), &d, comm, request);
+}
+
+/* coll_cuda_scan.c:41-76 / coll_cuda_exscan.c:41-76; rbuf is copied in for MPI_IN_PLACE and for
+ * exscan (rank 0's rbuf is left as it was, so a staged or joined copy must start from its contents) */
+static reduction_t red_scan(int exclusive, void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype,
+                            struct ompi_op_t *op)
+{
+    reduction_t d = red_count(RED_SCAN, sbuf, rbuf, count, dtype, op);
+    d.exclusive = exclusive;
+    d.rfill = d.inplace || exclusive;
+    return d;
+}
+
+int mca_coll_mi355x_scan(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
+                         struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    const reduction_t d = red_scan(0, sbuf, rbuf, count, dtype, op);
+    return reduction_blocking(MOD(module), &d, comm);
+}
+
+int mca_coll_mi355x_exscan(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
+                           struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    const reduction_t d = red_scan(1, sbuf, rbuf, count, dtype, op);
+    return reduction_blocking(MOD(module), &d, comm);
 }
 
 /* MPI_Iscan / MPI_Iexscan: in the reference coll/libnbc's, whose schedule copies through a host
  * tmpbuf and reduces with one host and one device operand (nbc_iscan.c:64-96, nbc_iexscan.c:69-126)
- * -- not usable on device buffers.  Shaped like iallreduce above; an exscan's rbuf is also filled
- * in (rank 0's is left as it was, so a staged or joined copy must start from its contents). */
-static int iscan_common(int exclusive, void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype,
-                        struct ompi_op_t *op, struct ompi_communicator_t *comm, ompi_request_t **request,
-                        mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    const int t = reducible_type(dtype);
-#define ISCAN_STAGED()                                                                                      \
-    do {                                                                                                    \
-        const size_t span = dt_span(dtype, (size_t)count);                                                  \
-        if (exclusive) NB_STAGED(iexscan, span, span, 1, span, dtype, sbuf, rbuf, count, dtype, op, comm);  \
-        NB_STAGED(iscan, span, span, inplace, span, dtype, sbuf, rbuf, count, dtype, op, comm);             \
-    } while (0)
-    if (count < 0) {
-        if (exclusive) NB_FALLBACK(iexscan, sbuf, rbuf, count, dtype, op, comm, request);
-        NB_FALLBACK(iscan, sbuf, rbuf, count, dtype, op, comm, request);
-    }
-    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
-    if (!engine_op(op, t) || (!dev && !m->mixed)) ISCAN_STAGED();
-    mi355x_request_t *eng = NULL;
-    if (!dev) {  /* host buffers: join the engine on device copies (nb_host_join) */
-        const size_t bytes = (size_t)count * mi355x_type_size(t);
-        struct nb_stage st;
-        void *sd, *rd;
-        int rc = nb_host_join(m, sbuf, rbuf, inplace, bytes, bytes, 1, &sd, &rd, &st);
-        if (rc == MI355X_SUCCESS && exclusive && !inplace && st.uhost && bytes) rc = mi355x_memcpy(rd, rbuf, bytes);
-        if (rc == MI355X_SUCCESS)
-            rc = (exclusive ? mi355x_iexscan : mi355x_iscan)(m->engine, sd, rd, (size_t)count, t, op->o_f_to_c_index, NULL,
-                                                             &eng);
-        if (rc == MI355X_SUCCESS) return nb_start_full(eng, comm, request, 0, &st);
-        nb_stage_release(&st);
-        if (!NB_UNFIT(rc)) return map_rc(rc);
-    } else {
-        int rc = (exclusive ? mi355x_iexscan : mi355x_iscan)(m->engine, inplace ? NULL : sbuf, rbuf, (size_t)count, t,
-                                                             op->o_f_to_c_index, NULL, &eng);
-        if (!NB_UNFIT(rc)) return rc ? map_rc(rc) : nb_start(eng, comm, request);
-    }
-    ISCAN_STAGED();
-#undef ISCAN_STAGED
-}
-
+ * -- not usable on device buffers */
 int mca_coll_mi355x_iscan(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
                           struct ompi_communicator_t *comm, ompi_request_t **request, mca_coll_base_module_t *module)
 {
-    return iscan_common(0, sbuf, rbuf, count, dtype, op, comm, request, module);
+    reduction_t d = red_scan(0, sbuf, rbuf, count, dtype, op);
+    d.no_prev = !MOD(module)->prev_iscan;
+    return reduction_nonblocking(MOD(module), &d, comm, request);
 }
 
 int mca_coll_mi355x_iexscan(void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
                             struct ompi_communicator_t *comm, ompi_request_t **request, mca_coll_base_module_t *module)
 {
-    return iscan_common(1, sbuf, rbuf, count, dtype, op, comm, request, module);
+    reduction_t d = red_scan(1, sbuf, rbuf, count, dtype, op);
+    d.no_prev = !MOD(module)->prev_iexscan;
+    return reduction_nonblocking(MOD(module), &d, comm, request);
 }
+
+/* ------------------------------------------------------------------ nonblocking movement */
 
 /* the (count, dt) side of a staged nonblocking move: pack it into `p` now (local work), or set up
  * the completion-time unpack into `st` (the request then owns a private layout of dt) */
@@ -1733,7 +1565,7 @@ int mca_coll_mi355x_iallgather(void *sbuf, int scount, struct ompi_datatype_t *s
     if (!rh && !sh && contiguous_bytes(rdtype, rcount, &rb) &&
         (inplace || (contiguous_bytes(sdtype, scount, &sb) && sb == rb))) {
         int rc = mi355x_iallgather(m->engine, inplace ? NULL : sbuf, rbuf, rb, NULL, &eng);
-        return rc ? map_rc(rc) : nb_start(eng, comm, request);
+        return rc ? map_rc(rc) : nb_start(eng, comm, request, 0, NULL);
     }
     /* derived layouts or host sides (a host rank joins the engine, nb_host_join): my block packed
      * into the per-request staging buffer now, the n blocks moved out of it at completion */
@@ -1767,7 +1599,7 @@ int mca_coll_mi355x_iallgather(void *sbuf, int scount, struct ompi_datatype_t *s
         nb_stage_release(&st);
         return map_rc(rc);
     }
-    return nb_start_full(eng, comm, request, 0, &st);
+    return nb_start(eng, comm, request, 0, &st);
 }
 
 /* derived layouts as in iallgather: the root packs at initiation, the others unpack at completion */
@@ -1781,7 +1613,7 @@ int mca_coll_mi355x_ibcast(void *buff, int count, struct ompi_datatype_t *dataty
     mi355x_request_t *eng = NULL;
     if (!host && contiguous_bytes(datatype, count, &bytes)) {
         int rc = mi355x_ibcast(m->engine, buff, bytes, root, NULL, &eng);
-        return rc ? map_rc(rc) : nb_start(eng, comm, request);
+        return rc ? map_rc(rc) : nb_start(eng, comm, request, 0, NULL);
     }
     const int me = mi355x_comm_rank_of(comm);
     struct nb_stage st = {NULL, (size_t)count * datatype->super.size, NULL, 0, NULL, NULL, 0};
@@ -1804,7 +1636,7 @@ int mca_coll_mi355x_ibcast(void *buff, int count, struct ompi_datatype_t *dataty
         nb_stage_release(&st);
         return map_rc(rc);
     }
-    return nb_start_full(eng, comm, request, 0, &st);
+    return nb_start(eng, comm, request, 0, &st);
 }
 
 /* ------------------------------------------------------------------ point-to-point (PML hook)
@@ -1869,7 +1701,7 @@ int mca_coll_mi355x_pml_isend(void *buf, size_t count, struct ompi_datatype_t *d
     if (rc) return rc;
     mi355x_request_t *eng = NULL;
     rc = mi355x_isend_mode(m->engine, buf, ec, d, dst, tag, (int)mode, NULL, &eng);
-    return rc ? map_rc(rc) : nb_start_kind(eng, comm, request, 1);
+    return rc ? map_rc(rc) : nb_start(eng, comm, request, 1, NULL);
 }
 
 /* synchronous sends complete once the receiver has the data; buffered and small sends once the
@@ -1897,7 +1729,7 @@ int mca_coll_mi355x_pml_irecv(void *buf, size_t count, struct ompi_datatype_t *d
     if (rc) return rc;
     mi355x_request_t *eng = NULL;
     rc = mi355x_irecv(m->engine, buf, ec, d, src, tag, NULL, &eng);
-    return rc ? map_rc(rc) : nb_start_kind(eng, comm, request, 2);
+    return rc ? map_rc(rc) : nb_start(eng, comm, request, 2, NULL);
 }
 
 int mca_coll_mi355x_pml_recv(void *buf, size_t count, struct ompi_datatype_t *dt, int src, int tag,
@@ -2011,7 +1843,7 @@ int mca_coll_mi355x_pml_imrecv(void *buf, size_t count, struct ompi_datatype_t *
     if (rc) return map_rc(rc);
     mi355x_obj_release(&(*message)->super.super);   /* ob1: ompi_message_return */
     *message = &ompi_message_null.message;
-    return nb_start_kind(eng, comm, request, 2);
+    return nb_start(eng, comm, request, 2, NULL);
 }
 
 int mca_coll_mi355x_pml_mrecv(void *buf, size_t count, struct ompi_datatype_t *dt, struct ompi_message_t **message,
@@ -2166,13 +1998,13 @@ static void pml_hook_remove(void)
 }
 
 /* ------------------------------------------------------------------ module / component */
-#define SNAP(FN)                                                                \
-    do {                                                                        \
-        m->prev_##FN = comm->c_coll.coll_##FN;                                  \
-        m->prev_##FN##_module = comm->c_coll.coll_##FN##_module;                \
-        if (!m->prev_##FN || !m->prev_##FN##_module) return OMPI_ERROR;         \
-        mi355x_obj_retain(&m->prev_##FN##_module->super);                       \
-    } while (0)
+/* snapshot a slot's previous owner; a slot that is not optional must have one.  Every module
+ * snapshotted is retained, and released in module_destruct */
+#define SNAP(FN, OPTIONAL)                                                                 \
+    m->prev_##FN = comm->c_coll.coll_##FN;                                                 \
+    m->prev_##FN##_module = comm->c_coll.coll_##FN##_module;                               \
+    if (m->prev_##FN##_module) mi355x_obj_retain(&m->prev_##FN##_module->super);           \
+    if (!(OPTIONAL) && (!m->prev_##FN || !m->prev_##FN##_module)) missing++;
 
 /* coll/tuned's own tuning, honoured so that a job tuned for the reference keeps its choices:
  * with coll_tuned_use_dynamic_rules set (coll_tuned_component.c:151-167), the forced algorithms
@@ -2240,13 +2072,6 @@ static void apply_tuned_params(mca_coll_mi355x_module_t *m)
     if (tuned_rules) mi355x_comm_set_rules(m->engine, tuned_rules);
 }
 
-#define SNAP_OPT(FN)                                                            \
-    do {                                                                        \
-        m->prev_##FN = comm->c_coll.coll_##FN;                                  \
-        m->prev_##FN##_module = comm->c_coll.coll_##FN##_module;                \
-        if (m->prev_##FN##_module) mi355x_obj_retain(&m->prev_##FN##_module->super); \
-    } while (0)
-
 /* The engine's crossovers as MCA variables, applied to each communicator's engine the way
  * coll/tuned applies its forced-algorithm variables per communicator (coll_tuned_module.c:178-226).
  * They are set before the engine's device-side setup runs (it waits for the first device-buffer
@@ -2294,29 +2119,9 @@ struct mi355x_comm *mca_coll_mi355x_engine_of(struct ompi_communicator_t *comm)
 static int module_enable(mca_coll_base_module_t *module, struct ompi_communicator_t *comm)
 {
     mca_coll_mi355x_module_t *m = MOD(module);
-    SNAP(allreduce);
-    SNAP(reduce_scatter);
-    SNAP(reduce_scatter_block);
-    SNAP(allgather);
-    SNAP(bcast);
-    SNAP(reduce);
-    SNAP(gather);
-    SNAP(gatherv);
-    SNAP(scatter);
-    SNAP(scatterv);
-    SNAP(allgatherv);
-    SNAP(alltoall);
-    SNAP(alltoallv);
-    SNAP(scan);
-    SNAP(exscan);
-    SNAP_OPT(iallreduce);
-    SNAP_OPT(ireduce);
-    SNAP_OPT(ireduce_scatter_block);
-    SNAP_OPT(ireduce_scatter);
-    SNAP_OPT(iallgather);
-    SNAP_OPT(ibcast);
-    SNAP_OPT(iscan);
-    SNAP_OPT(iexscan);
+    int missing = 0;
+    COLL_SLOTS(SNAP)
+    if (missing) return OMPI_ERROR;
     /* Node-unique rendezvous key, picked by rank 0 and broadcast with the lower-priority bcast
      * just snapshotted (the communicator is p2p-capable during enable, coll.h:125-127).  Neither
      * the job id nor the context id would do: MPI_Comm_split allocates ONE cid for every color
@@ -2473,29 +2278,9 @@ static mca_coll_base_module_t *component_comm_query(struct ompi_communicator_t *
     mca_coll_mi355x_module_t *m = (mca_coll_mi355x_module_t *)mi355x_obj_new(&mca_coll_mi355x_module_t_class);
     if (!m) return NULL;
     m->super.coll_module_enable = module_enable;
-    m->super.coll_allreduce = mca_coll_mi355x_allreduce;
-    m->super.coll_reduce_scatter = mca_coll_mi355x_reduce_scatter;
-    m->super.coll_reduce_scatter_block = mca_coll_mi355x_reduce_scatter_block;
-    m->super.coll_allgather = mca_coll_mi355x_allgather;
-    m->super.coll_bcast = mca_coll_mi355x_bcast;
-    m->super.coll_reduce = mca_coll_mi355x_reduce;
-    m->super.coll_gather = mca_coll_mi355x_gather;
-    m->super.coll_gatherv = mca_coll_mi355x_gatherv;
-    m->super.coll_scatter = mca_coll_mi355x_scatter;
-    m->super.coll_scatterv = mca_coll_mi355x_scatterv;
-    m->super.coll_allgatherv = mca_coll_mi355x_allgatherv;
-    m->super.coll_alltoall = mca_coll_mi355x_alltoall;
-    m->super.coll_alltoallv = mca_coll_mi355x_alltoallv;
-    m->super.coll_scan = mca_coll_mi355x_scan;
-    m->super.coll_exscan = mca_coll_mi355x_exscan;
-    m->super.coll_iallreduce = mca_coll_mi355x_iallreduce;
-    m->super.coll_iscan = mca_coll_mi355x_iscan;
-    m->super.coll_iexscan = mca_coll_mi355x_iexscan;
-    m->super.coll_ireduce = mca_coll_mi355x_ireduce;
-    m->super.coll_ireduce_scatter_block = mca_coll_mi355x_ireduce_scatter_block;
-    m->super.coll_ireduce_scatter = mca_coll_mi355x_ireduce_scatter;
-    m->super.coll_iallgather = mca_coll_mi355x_iallgather;
-    m->super.coll_ibcast = mca_coll_mi355x_ibcast;
+#define OWN(FN, OPTIONAL) m->super.coll_##FN = mca_coll_mi355x_##FN;
+    COLL_SLOTS(OWN)
+#undef OWN
     m->super.ft_event = NULL;
     *priority = mca_coll_mi355x_priority > 100 ? 100 : mca_coll_mi355x_priority;
     return &m->super;
