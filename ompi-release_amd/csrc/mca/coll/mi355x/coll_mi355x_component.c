@@ -339,16 +339,6 @@ static int copy_back(void *host, const void *dev, size_t bytes, int rc)
     return mi355x_memcpy(host, dev, bytes);
 }
 
-/* PREV_CALL: the previous component on this rank's own (host) buffers; STAGED_CALL: the same with
- * this rank's device buffers staged through host memory (a device rank in a call that runs on the
- * host) */
-#define ROUTE_OR(PREV_CALL, STAGED_CALL)                                               \
-    do {                                                                               \
-        const int r_ = route(m, dev);                                                  \
-        if (r_ < 0) return OMPI_ERROR;                                                 \
-        if (r_ == 0) return dev ? (STAGED_CALL) : (PREV_CALL);                         \
-    } while (0)
-
 /* ------------------------------------------------------------------ coll/cuda's host staging
  * A reduction the engine declines -- a user-defined MPI_Op, or a type with no engine slot (the x87
  * long double slots the engine has no fold for) -- goes to the lower-priority component, which
@@ -404,12 +394,14 @@ static int hunstage(hstage_t *s, int rc)
     return rc;
 }
 
-/* stage the send and receive sides of a reduction; on failure nothing stays staged */
-static int hstage2(hstage_t st[2], void **sa, size_t sspan, void **ra, size_t rspan, int rfill, size_t rback,
-                   const struct ompi_datatype_t *dt)
+/* stage the send and receive sides of a call (sa / ra NULL: that side is not significant on this
+ * rank); on failure nothing stays staged.  A call with a side staged counts once. */
+static int hstage2(hstage_t st[2], void **sa, const struct ompi_datatype_t *sdt, size_t sspan, void **ra,
+                   const struct ompi_datatype_t *rdt, size_t rspan, int rfill, size_t rback)
 {
-    int rc = hstage(&st[0], sa, dt, sspan, 1, 0);
-    if (rc == OMPI_SUCCESS && (rc = hstage(&st[1], ra, dt, rspan, rfill, rback)) != OMPI_SUCCESS) hunstage(&st[0], rc);
+    memset(st, 0, 2 * sizeof(hstage_t));
+    int rc = sa ? hstage(&st[0], sa, sdt, sspan, 1, 0) : OMPI_SUCCESS;
+    if (rc == OMPI_SUCCESS && ra && (rc = hstage(&st[1], ra, rdt, rspan, rfill, rback)) != OMPI_SUCCESS) hunstage(&st[0], rc);
     if (rc == OMPI_SUCCESS && (st[0].h || st[1].h)) __atomic_add_fetch(&mca_coll_mi355x_staged_calls, 1, __ATOMIC_RELAXED);
     return rc;
 }
@@ -424,20 +416,6 @@ static int hunstage2(hstage_t st[2], int rc)
 static int engine_op(const struct ompi_op_t *op, int t)
 {
     return (op->o_flags & OMPI_OP_FLAGS_INTRINSIC) && t >= 0 && mi355x_comm_op_supported(op->o_f_to_c_index, t);
-}
-
-/* the send and receive sides of a data-movement call staged to the host (coll/cuda's rule applied
- * to the movement collectives): the send span copied in; the receive span copied in too (its gaps
- * keep their bytes) and back after the call.  A side is (buffer, type, span); NULL / MPI_IN_PLACE /
- * host buffers are left alone. */
-static int stage_move(hstage_t st[2], void **sa, const struct ompi_datatype_t *sdt, size_t sspan, void **ra,
-                      const struct ompi_datatype_t *rdt, size_t rspan)
-{
-    memset(st, 0, 2 * sizeof(hstage_t));
-    int rc = sa ? hstage(&st[0], sa, sdt, sspan, 1, 0) : OMPI_SUCCESS;
-    if (rc == OMPI_SUCCESS && ra && (rc = hstage(&st[1], ra, rdt, rspan, 1, rspan)) != OMPI_SUCCESS) hunstage(&st[0], rc);
-    if (rc == OMPI_SUCCESS && (st[0].h || st[1].h)) __atomic_add_fetch(&mca_coll_mi355x_staged_calls, 1, __ATOMIC_RELAXED);
-    return rc;
 }
 
 /* bytes spanned by piece q = counts[q] instances at disps[q] extents (NULL disps: consecutive),
@@ -459,42 +437,15 @@ static size_t vspan(const struct ompi_datatype_t *dt, int n, const int *counts, 
     return best;
 }
 
-/* ------------------------------------------------------------------ collectives */
-static int staged_allgather(mca_coll_mi355x_module_t *m, void *sbuf, int scount, struct ompi_datatype_t *sdtype,
+/* ------------------------------------------------------------------ collectives
+ * The engine steps of the movement calls (their drivers: "data movement", below).  allgather and bcast
+ * have their own: a contiguous device layout goes straight to the engine, a derived one through one
+ * scratch buffer, a rank on host buffers (!dev) joins on device copies. */
+static int allgather_engine(mca_coll_mi355x_module_t *m, int dev, void *sbuf, int scount, struct ompi_datatype_t *sdtype,
                             void *rbuf, int rcount, struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm)
 {
-    hstage_t st[2];
-    void *s = sbuf, *r = rbuf;
-    int rc = stage_move(st, &s, sdtype, dt_span(sdtype, (size_t)scount), &r, rdtype,
-                        dt_span(rdtype, (size_t)rcount * (size_t)mi355x_comm_size_of(comm)));
-    if (rc != OMPI_SUCCESS) return rc;
-    return hunstage2(st, m->prev_allgather(s, scount, sdtype, r, rcount, rdtype, comm, m->prev_allgather_module));
-}
-
-static int staged_bcast(mca_coll_mi355x_module_t *m, void *buff, int count, struct ompi_datatype_t *datatype, int root,
-                        struct ompi_communicator_t *comm)
-{
-    hstage_t st[2];
-    void *b = buff;
-    const size_t span = dt_span(datatype, (size_t)count);
-    const int me = mi355x_comm_rank_of(comm);
-    int rc = me == root ? stage_move(st, &b, datatype, span, NULL, NULL, 0) : stage_move(st, NULL, NULL, 0, &b, datatype, span);
-    if (rc != OMPI_SUCCESS) return rc;
-    return hunstage2(st, m->prev_bcast(b, count, datatype, root, comm, m->prev_bcast_module));
-}
-
-int mca_coll_mi355x_allgather(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
-                              struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
-                              mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
     const int inplace = (sbuf == MPI_IN_PLACE);
-    if (rcount < 0 || (!inplace && scount < 0))
-        return m->prev_allgather(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, m->prev_allgather_module);
-    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
     const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm);
-    ROUTE_OR(m->prev_allgather(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, m->prev_allgather_module),
-             staged_allgather(m, sbuf, scount, sdtype, rbuf, rcount, rdtype, comm));
     size_t rb = 0, sb = 0;
     if (!dev) {  /* host buffers in a call where peers hold device ones: dense layouts, staged */
         if (!contiguous_bytes(rdtype, rcount, &rb) || (!inplace && (!contiguous_bytes(sdtype, scount, &sb) || sb != rb))) {
@@ -532,15 +483,10 @@ int mca_coll_mi355x_allgather(void *sbuf, int scount, struct ompi_datatype_t *sd
     return map_rc(rc);
 }
 
-int mca_coll_mi355x_bcast(void *buff, int count, struct ompi_datatype_t *datatype, int root,
-                          struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+static int bcast_engine(mca_coll_mi355x_module_t *m, int dev, void *buff, int count, struct ompi_datatype_t *datatype,
+                        int root, struct ompi_communicator_t *comm)
 {
-    mca_coll_mi355x_module_t *m = MOD(module);
     size_t bytes = 0;
-    if (count < 0) return m->prev_bcast(buff, count, datatype, root, comm, m->prev_bcast_module);
-    const int dev = is_dev(buff);
-    ROUTE_OR(m->prev_bcast(buff, count, datatype, root, comm, m->prev_bcast_module),
-             staged_bcast(m, buff, count, datatype, root, comm));
     const int me = mi355x_comm_rank_of(comm);
     if (!dev) {  /* host buffer in a call where peers hold device ones: dense layouts, staged */
         if (!contiguous_bytes(datatype, count, &bytes)) {
@@ -654,222 +600,6 @@ static int side_move(mca_coll_mi355x_module_t *m, side_t *s, int q, int pack)
         if (rc) return rc;
     }
     return MI355X_SUCCESS;
-}
-
-static int finish_unpack(mca_coll_mi355x_module_t *m, side_t *s, int rc)
-{
-    if (rc == MI355X_SUCCESS && s && (s->d || s->host)) {
-        rc = side_move(m, s, -1, 0);
-        if (rc == MI355X_SUCCESS) rc = mi355x_stream_sync(NULL);
-    }
-    return map_rc(rc);
-}
-
-int mca_coll_mi355x_gather(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
-                           struct ompi_datatype_t *rdtype, int root, struct ompi_communicator_t *comm,
-                           mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm), inplace = (sbuf == MPI_IN_PLACE);
-    if (inplace && me != root)
-        return m->prev_gather(sbuf, scount, sdtype, rbuf, rcount, rdtype, root, comm, m->prev_gather_module);
-    const int dev = (me != root || is_dev(rbuf)) && (inplace || is_dev(sbuf));
-    ROUTE_OR(m->prev_gather(sbuf, scount, sdtype, rbuf, rcount, rdtype, root, comm, m->prev_gather_module), ({
-                 hstage_t st_[2];
-                 void *s_ = sbuf, *r_ = rbuf;
-                 int rc_ = stage_move(st_, inplace ? NULL : &s_, sdtype, dt_span(sdtype, (size_t)scount),
-                                      me == root ? &r_ : NULL, rdtype, dt_span(rdtype, (size_t)rcount * (size_t)n));
-                 rc_ == OMPI_SUCCESS ? hunstage2(st_, m->prev_gather(s_, scount, sdtype, r_, rcount, rdtype, root, comm,
-                                                                     m->prev_gather_module)) : rc_;
-             }));
-    side_t snd, rcv;
-    int rc = OMPI_SUCCESS;
-    if (!inplace && (rc = side_init(m, &snd, 0, sbuf, sdtype, 1, NULL, scount, NULL))) return rc;
-    if (me == root && (rc = side_init(m, &rcv, 1, rbuf, rdtype, n, NULL, rcount, NULL))) return rc;
-    const size_t bytes = inplace ? rcv.bytes[me] : snd.bytes[0];
-    int erc = inplace ? side_move(m, &rcv, me, 1) : side_move(m, &snd, 0, 1);
-    if (erc == MI355X_SUCCESS)
-        erc = mi355x_gather(m->engine, inplace ? NULL : snd.view, me == root ? rcv.view : NULL, bytes, root, NULL);
-    return finish_unpack(m, me == root ? &rcv : NULL, erc);
-}
-
-int mca_coll_mi355x_gatherv(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int *rcounts,
-                            int *disps, struct ompi_datatype_t *rdtype, int root, struct ompi_communicator_t *comm,
-                            mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm), inplace = (sbuf == MPI_IN_PLACE);
-    if (n > SIDE_MAX || (inplace && me != root))
-        return m->prev_gatherv(sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype, root, comm, m->prev_gatherv_module);
-    const int dev = (me != root || is_dev(rbuf)) && (inplace || is_dev(sbuf));
-    ROUTE_OR(m->prev_gatherv(sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype, root, comm, m->prev_gatherv_module), ({
-                 hstage_t st_[2];
-                 void *s_ = sbuf, *r_ = rbuf;
-                 const size_t rs_ = me == root ? vspan(rdtype, n, rcounts, disps) : 0;
-                 int rc_ = rs_ == (size_t)-1 ? OMPI_ERR_NOT_SUPPORTED
-                                             : stage_move(st_, inplace ? NULL : &s_, sdtype, dt_span(sdtype, (size_t)scount),
-                                                          me == root ? &r_ : NULL, rdtype, rs_);
-                 rc_ == OMPI_SUCCESS ? hunstage2(st_, m->prev_gatherv(s_, scount, sdtype, r_, rcounts, disps, rdtype, root,
-                                                                      comm, m->prev_gatherv_module)) : rc_;
-             }));
-    side_t snd, rcv;
-    int rc = OMPI_SUCCESS;
-    if (!inplace && (rc = side_init(m, &snd, 0, sbuf, sdtype, 1, NULL, scount, NULL))) return rc;
-    if (me == root && (rc = side_init(m, &rcv, 1, rbuf, rdtype, n, rcounts, 0, disps))) return rc;
-    int erc = inplace ? side_move(m, &rcv, me, 1) : side_move(m, &snd, 0, 1);
-    if (erc == MI355X_SUCCESS)
-        erc = mi355x_gatherv(m->engine, inplace ? NULL : snd.view, inplace ? 0 : snd.bytes[0],
-                             me == root ? rcv.view : NULL, me == root ? rcv.bytes : NULL,
-                             me == root ? rcv.off : NULL, root, NULL);
-    return finish_unpack(m, me == root ? &rcv : NULL, erc);
-}
-
-int mca_coll_mi355x_scatter(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
-                            struct ompi_datatype_t *rdtype, int root, struct ompi_communicator_t *comm,
-                            mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm), inplace = (rbuf == MPI_IN_PLACE);
-    if (inplace && me != root)
-        return m->prev_scatter(sbuf, scount, sdtype, rbuf, rcount, rdtype, root, comm, m->prev_scatter_module);
-    const int dev = (me != root || is_dev(sbuf)) && (inplace || is_dev(rbuf));
-    ROUTE_OR(m->prev_scatter(sbuf, scount, sdtype, rbuf, rcount, rdtype, root, comm, m->prev_scatter_module), ({
-                 hstage_t st_[2];
-                 void *s_ = sbuf, *r_ = rbuf;
-                 int rc_ = stage_move(st_, me == root ? &s_ : NULL, sdtype, dt_span(sdtype, (size_t)scount * (size_t)n),
-                                      inplace ? NULL : &r_, rdtype, dt_span(rdtype, (size_t)rcount));
-                 rc_ == OMPI_SUCCESS ? hunstage2(st_, m->prev_scatter(s_, scount, sdtype, r_, rcount, rdtype, root, comm,
-                                                                      m->prev_scatter_module)) : rc_;
-             }));
-    side_t snd, rcv;
-    int rc = OMPI_SUCCESS;
-    if (me == root && (rc = side_init(m, &snd, 0, sbuf, sdtype, n, NULL, scount, NULL))) return rc;
-    if (!inplace && (rc = side_init(m, &rcv, 1, rbuf, rdtype, 1, NULL, rcount, NULL))) return rc;
-    const size_t bytes = me == root ? snd.bytes[0] : rcv.bytes[0];
-    int erc = me == root ? side_move(m, &snd, -1, 1) : MI355X_SUCCESS;
-    if (erc == MI355X_SUCCESS)
-        erc = mi355x_scatter(m->engine, me == root ? snd.view : NULL, inplace ? NULL : rcv.view, bytes, root, NULL);
-    return finish_unpack(m, inplace ? NULL : &rcv, erc);
-}
-
-int mca_coll_mi355x_scatterv(void *sbuf, int *scounts, int *disps, struct ompi_datatype_t *sdtype, void *rbuf,
-                             int rcount, struct ompi_datatype_t *rdtype, int root, struct ompi_communicator_t *comm,
-                             mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm), inplace = (rbuf == MPI_IN_PLACE);
-    if (n > SIDE_MAX || (inplace && me != root))
-        return m->prev_scatterv(sbuf, scounts, disps, sdtype, rbuf, rcount, rdtype, root, comm,
-                                m->prev_scatterv_module);
-    const int dev = (me != root || is_dev(sbuf)) && (inplace || is_dev(rbuf));
-    ROUTE_OR(m->prev_scatterv(sbuf, scounts, disps, sdtype, rbuf, rcount, rdtype, root, comm, m->prev_scatterv_module), ({
-                 hstage_t st_[2];
-                 void *s_ = sbuf, *r_ = rbuf;
-                 const size_t ss_ = me == root ? vspan(sdtype, n, scounts, disps) : 0;
-                 int rc_ = ss_ == (size_t)-1 ? OMPI_ERR_NOT_SUPPORTED
-                                             : stage_move(st_, me == root ? &s_ : NULL, sdtype, ss_, inplace ? NULL : &r_,
-                                                          rdtype, dt_span(rdtype, (size_t)rcount));
-                 rc_ == OMPI_SUCCESS ? hunstage2(st_, m->prev_scatterv(s_, scounts, disps, sdtype, r_, rcount, rdtype, root,
-                                                                       comm, m->prev_scatterv_module)) : rc_;
-             }));
-    side_t snd, rcv;
-    int rc = OMPI_SUCCESS;
-    if (me == root && (rc = side_init(m, &snd, 0, sbuf, sdtype, n, scounts, 0, disps))) return rc;
-    if (!inplace && (rc = side_init(m, &rcv, 1, rbuf, rdtype, 1, NULL, rcount, NULL))) return rc;
-    int erc = me == root ? side_move(m, &snd, -1, 1) : MI355X_SUCCESS;
-    if (erc == MI355X_SUCCESS)
-        erc = mi355x_scatterv(m->engine, me == root ? snd.view : NULL, me == root ? snd.bytes : NULL,
-                              me == root ? snd.off : NULL, inplace ? NULL : rcv.view, inplace ? 0 : rcv.bytes[0], root,
-                              NULL);
-    return finish_unpack(m, inplace ? NULL : &rcv, erc);
-}
-
-int mca_coll_mi355x_allgatherv(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int *rcounts,
-                               int *disps, struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
-                               mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm), inplace = (sbuf == MPI_IN_PLACE);
-    if (n > SIDE_MAX)
-        return m->prev_allgatherv(sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype, comm, m->prev_allgatherv_module);
-    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
-    ROUTE_OR(m->prev_allgatherv(sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype, comm, m->prev_allgatherv_module), ({
-                 hstage_t st_[2];
-                 void *s_ = sbuf, *r_ = rbuf;
-                 const size_t rs_ = vspan(rdtype, n, rcounts, disps);
-                 int rc_ = rs_ == (size_t)-1 ? OMPI_ERR_NOT_SUPPORTED
-                                             : stage_move(st_, inplace ? NULL : &s_, sdtype, dt_span(sdtype, (size_t)scount),
-                                                          &r_, rdtype, rs_);
-                 rc_ == OMPI_SUCCESS ? hunstage2(st_, m->prev_allgatherv(s_, scount, sdtype, r_, rcounts, disps, rdtype, comm,
-                                                                         m->prev_allgatherv_module)) : rc_;
-             }));
-    side_t snd, rcv;
-    int rc = OMPI_SUCCESS;
-    if (!inplace && (rc = side_init(m, &snd, 0, sbuf, sdtype, 1, NULL, scount, NULL))) return rc;
-    if ((rc = side_init(m, &rcv, 1, rbuf, rdtype, n, rcounts, 0, disps))) return rc;
-    int erc = inplace ? side_move(m, &rcv, me, 1) : side_move(m, &snd, 0, 1);
-    if (erc == MI355X_SUCCESS)
-        erc = mi355x_allgatherv(m->engine, inplace ? NULL : snd.view, inplace ? 0 : snd.bytes[0], rcv.view, rcv.bytes,
-                                rcv.off, NULL);
-    return finish_unpack(m, &rcv, erc);
-}
-
-int mca_coll_mi355x_alltoall(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
-                             struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
-                             mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int n = mi355x_comm_size_of(comm), inplace = (sbuf == MPI_IN_PLACE);
-    if (n > SIDE_MAX) return m->prev_alltoall(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, m->prev_alltoall_module);
-    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
-    ROUTE_OR(m->prev_alltoall(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, m->prev_alltoall_module), ({
-                 hstage_t st_[2];
-                 void *s_ = sbuf, *r_ = rbuf;
-                 int rc_ = stage_move(st_, inplace ? NULL : &s_, sdtype, dt_span(sdtype, (size_t)scount * (size_t)n), &r_,
-                                      rdtype, dt_span(rdtype, (size_t)rcount * (size_t)n));
-                 rc_ == OMPI_SUCCESS ? hunstage2(st_, m->prev_alltoall(s_, scount, sdtype, r_, rcount, rdtype, comm,
-                                                                       m->prev_alltoall_module)) : rc_;
-             }));
-    side_t snd, rcv;
-    int rc = OMPI_SUCCESS;
-    if (!inplace && (rc = side_init(m, &snd, 0, sbuf, sdtype, n, NULL, scount, NULL))) return rc;
-    if ((rc = side_init(m, &rcv, 1, rbuf, rdtype, n, NULL, rcount, NULL))) return rc;
-    if (!inplace && snd.bytes[0] != rcv.bytes[0]) return OMPI_ERR_BAD_PARAM;
-    int erc = inplace ? side_move(m, &rcv, -1, 1) : side_move(m, &snd, -1, 1);
-    if (erc == MI355X_SUCCESS) erc = mi355x_alltoall(m->engine, inplace ? NULL : snd.view, rcv.view, rcv.bytes[0], NULL);
-    return finish_unpack(m, &rcv, erc);
-}
-
-int mca_coll_mi355x_alltoallv(void *sbuf, int *scounts, int *sdisps, struct ompi_datatype_t *sdtype, void *rbuf,
-                              int *rcounts, int *rdisps, struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
-                              mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int n = mi355x_comm_size_of(comm), inplace = (sbuf == MPI_IN_PLACE);
-    if (n > SIDE_MAX)
-        return m->prev_alltoallv(sbuf, scounts, sdisps, sdtype, rbuf, rcounts, rdisps, rdtype, comm,
-                                 m->prev_alltoallv_module);
-    const int dev = is_dev(rbuf) && (inplace || is_dev(sbuf));
-    ROUTE_OR(m->prev_alltoallv(sbuf, scounts, sdisps, sdtype, rbuf, rcounts, rdisps, rdtype, comm,
-                               m->prev_alltoallv_module), ({
-                 hstage_t st_[2];
-                 void *s_ = sbuf, *r_ = rbuf;
-                 const size_t ss_ = inplace ? 0 : vspan(sdtype, n, scounts, sdisps), rs_ = vspan(rdtype, n, rcounts, rdisps);
-                 int rc_ = (ss_ == (size_t)-1 || rs_ == (size_t)-1)
-                               ? OMPI_ERR_NOT_SUPPORTED
-                               : stage_move(st_, inplace ? NULL : &s_, sdtype, ss_, &r_, rdtype, rs_);
-                 rc_ == OMPI_SUCCESS ? hunstage2(st_, m->prev_alltoallv(s_, scounts, sdisps, sdtype, r_, rcounts, rdisps,
-                                                                        rdtype, comm, m->prev_alltoallv_module)) : rc_;
-             }));
-    side_t snd, rcv;
-    int rc = OMPI_SUCCESS;
-    if (!inplace && (rc = side_init(m, &snd, 0, sbuf, sdtype, n, scounts, 0, sdisps))) return rc;
-    if ((rc = side_init(m, &rcv, 1, rbuf, rdtype, n, rcounts, 0, rdisps))) return rc;
-    int erc = inplace ? side_move(m, &rcv, -1, 1) : side_move(m, &snd, -1, 1);
-    if (erc == MI355X_SUCCESS)
-        erc = mi355x_alltoallv(m->engine, inplace ? NULL : snd.view, inplace ? NULL : snd.bytes,
-                               inplace ? NULL : snd.off, rcv.view, rcv.bytes, rcv.off, NULL);
-    return finish_unpack(m, &rcv, erc);
 }
 
 /* ------------------------------------------------------------------ nonblocking collectives
@@ -1105,12 +835,6 @@ static int nb_start(mi355x_request_t *eng, struct ompi_communicator_t *comm, omp
     return nb_launch(r, comm, request);
 }
 
-#define NB_FALLBACK(FN, ...)                                                          \
-    do {                                                                              \
-        if (!m->prev_##FN) return OMPI_ERR_NOT_SUPPORTED;                             \
-        return m->prev_##FN(__VA_ARGS__, m->prev_##FN##_module);                      \
-    } while (0)
-
 /* hand the lower-priority component's request to MPI: as it is when nothing was staged, else
  * wrapped so that the staged results are copied back when it completes (nb_progress) */
 static int nb_staged_start(struct ompi_communicator_t *comm, ompi_request_t **request, hstage_t st[2],
@@ -1132,6 +856,405 @@ static int nb_staged_start(struct ompi_communicator_t *comm, ompi_request_t **re
     r->hs[0] = st[0];
     r->hs[1] = st[1];
     return nb_launch(r, comm, request);
+}
+
+/* the (count, dt) side of a staged nonblocking move: pack it into `p` now (local work), or set up
+ * the completion-time unpack into `st` (the request then owns a private layout of dt) */
+static int nb_stage_side(int pack, void *buf, size_t count, const struct ompi_datatype_t *dt, void *p, size_t bytes,
+                         struct nb_stage *st)
+{
+    size_t cb;
+    if (contiguous_bytes_n(dt, count, &cb)) {
+        if (pack) return mi355x_memcpy_async(p, buf, bytes, NULL);
+        st->ubuf = buf;
+        return MI355X_SUCCESS;
+    }
+    mi355x_ddt_t *d = ddt_private(dt);
+    if (!d) return MI355X_ERR_UNSUPPORTED;
+    if (pack) {
+        st->pd = d;  /* the pack kernel reads its run tables until it finishes: released at completion */
+        return mi355x_pack(d, count, buf, 0, p, bytes, NULL, NULL);
+    }
+    st->ubuf = buf;
+    st->ucount = count;
+    st->ud = d;
+    return MI355X_SUCCESS;
+}
+
+/* Contiguous layouts go straight to the engine.  Derived layouts -- on any rank, whatever the
+ * others use (MPI lets layouts differ; only the type signatures match) -- also stay in the
+ * engine: my block is packed into a per-request staging buffer at initiation, the engine gathers
+ * the packed blocks in place, and the completion unpacks them into rbuf (all local work, so the
+ * call stays nonblocking); rank-local fallbacks to libnbc would leave the ranks in different
+ * components. */
+static int iallgather_engine(mca_coll_mi355x_module_t *m, void *sbuf, int scount, struct ompi_datatype_t *sdtype,
+                             void *rbuf, int rcount, struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
+                             ompi_request_t **request)
+{
+    const int inplace = (sbuf == MPI_IN_PLACE);
+    size_t rb = 0, sb = 0;
+    const int rh = !is_dev(rbuf), sh = !inplace && !is_dev(sbuf);
+    mi355x_request_t *eng = NULL;
+    if (!rh && !sh && contiguous_bytes(rdtype, rcount, &rb) &&
+        (inplace || (contiguous_bytes(sdtype, scount, &sb) && sb == rb))) {
+        int rc = mi355x_iallgather(m->engine, inplace ? NULL : sbuf, rbuf, rb, NULL, &eng);
+        return rc ? map_rc(rc) : nb_start(eng, comm, request, 0, NULL);
+    }
+    /* derived layouts or host sides (a host rank joins the engine, nb_host_join): my block packed
+     * into the per-request staging buffer now, the n blocks moved out of it at completion */
+    const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm);
+    const size_t blk = (size_t)rcount * rdtype->super.size;
+    if (!inplace && (size_t)scount * sdtype->super.size != blk) return OMPI_ERR_BAD_PARAM;
+    struct nb_stage st = {NULL, blk * (size_t)n, NULL, 0, NULL, NULL, 0};
+    if (mi355x_malloc(&st.stage, st.bytes ? st.bytes : 1) != MI355X_SUCCESS) return OMPI_ERR_OUT_OF_RESOURCE;
+    const ptrdiff_t rext = rdtype->super.ub - rdtype->super.lb;
+    int rc;
+    if (inplace && rh)
+        rc = xstage(m, 1, (char *)rbuf + (ptrdiff_t)me * rcount * rext, rcount, rdtype, (char *)st.stage + blk * me, blk, 1);
+    else if (sh)
+        rc = xstage(m, 1, sbuf, scount, sdtype, (char *)st.stage + blk * me, blk, 1);
+    else
+        rc = inplace ? nb_stage_side(1, (char *)rbuf + (ptrdiff_t)me * rcount * rext, rcount, rdtype,
+                                     (char *)st.stage + blk * me, blk, &st)
+                     : nb_stage_side(1, sbuf, scount, sdtype, (char *)st.stage + blk * me, blk, &st);
+    if (rc == MI355X_SUCCESS && rh) {
+        st.ubuf = rbuf;
+        st.ucount = (size_t)rcount * (size_t)n;
+        st.uhost = 1;
+        if (!contiguous_bytes_n(rdtype, st.ucount, &rb) && !(st.ud = ddt_private(rdtype))) rc = MI355X_ERR_UNSUPPORTED;
+    } else if (rc == MI355X_SUCCESS) {
+        rc = nb_stage_side(0, rbuf, (size_t)rcount * (size_t)n, rdtype, st.stage, st.bytes, &st);
+    }
+    if (rc == MI355X_SUCCESS) rc = mi355x_iallgather(m->engine, NULL, st.stage, blk, NULL, &eng);
+    if (rc != MI355X_SUCCESS) {
+        if (rc == MI355X_ERR_UNSUPPORTED)
+            fprintf(stderr, "[coll/mi355x] iallgather: the GPU convertor cannot describe the datatype\n");
+        nb_stage_release(&st);
+        return map_rc(rc);
+    }
+    return nb_start(eng, comm, request, 0, &st);
+}
+
+/* derived layouts as in iallgather: the root packs at initiation, the others unpack at completion */
+static int ibcast_engine(mca_coll_mi355x_module_t *m, void *buff, int count, struct ompi_datatype_t *datatype, int root,
+                         struct ompi_communicator_t *comm, ompi_request_t **request)
+{
+    size_t bytes = 0;
+    const int host = !is_dev(buff);
+    mi355x_request_t *eng = NULL;
+    if (!host && contiguous_bytes(datatype, count, &bytes)) {
+        int rc = mi355x_ibcast(m->engine, buff, bytes, root, NULL, &eng);
+        return rc ? map_rc(rc) : nb_start(eng, comm, request, 0, NULL);
+    }
+    const int me = mi355x_comm_rank_of(comm);
+    struct nb_stage st = {NULL, (size_t)count * datatype->super.size, NULL, 0, NULL, NULL, 0};
+    if (mi355x_malloc(&st.stage, st.bytes ? st.bytes : 1) != MI355X_SUCCESS) return OMPI_ERR_OUT_OF_RESOURCE;
+    int rc = MI355X_SUCCESS;
+    if (!host) {
+        rc = nb_stage_side(me == root, buff, count, datatype, st.stage, st.bytes, &st);
+    } else if (me == root) {  /* a host rank joining the engine (nb_host_join): packed / copied now */
+        rc = xstage(m, 1, buff, (size_t)count, datatype, st.stage, st.bytes, 1);
+    } else {                  /* ... or moved out of the staging buffer at completion */
+        st.ubuf = buff;
+        st.ucount = (size_t)count;
+        st.uhost = 1;
+        if (!contiguous_bytes(datatype, count, &bytes) && !(st.ud = ddt_private(datatype))) rc = MI355X_ERR_UNSUPPORTED;
+    }
+    if (rc == MI355X_SUCCESS) rc = mi355x_ibcast(m->engine, st.stage, st.bytes, root, NULL, &eng);
+    if (rc != MI355X_SUCCESS) {
+        if (rc == MI355X_ERR_UNSUPPORTED)
+            fprintf(stderr, "[coll/mi355x] ibcast: the GPU convertor cannot describe datatype %s\n", datatype->name);
+        nb_stage_release(&st);
+        return map_rc(rc);
+    }
+    return nb_start(eng, comm, request, 0, &st);
+}
+
+/* ------------------------------------------------------------------ data movement
+ * allgather(v), bcast, gather(v), scatter(v) and alltoall(v), and the nonblocking allgather and bcast:
+ * each entry point describes the call and hands the description to one of two drivers, which hold the
+ * decision ladder once:
+ *   1. a bad argument goes to the previous owner as it is;
+ *   2. the route: the buffer-kind vote (blocking), the mixed switch (nonblocking);
+ *   3. a call the route gives to the host runs in the previous owner, this rank's device buffers staged
+ *      through host memory;
+ *   4. otherwise the engine step: the sides are set up, packed, moved and unpacked (above). */
+enum move_kind { MOVE_ALLGATHER, MOVE_BCAST, MOVE_GATHER, MOVE_GATHERV, MOVE_SCATTER, MOVE_SCATTERV, MOVE_ALLGATHERV,
+                 MOVE_ALLTOALL, MOVE_ALLTOALLV };
+
+/* one side of a call, in the caller's own arguments (the previous owner gets them as they are) */
+typedef struct {
+    void *buf;       /* MPI_IN_PLACE included */
+    struct ompi_datatype_t *dt;
+    int sig;         /* significant on this rank: else never looked at, staged or handed to the engine */
+    int n;           /* pieces: 1, or one per rank (0 until movement() knows how many) */
+    int count;       /* instances in every piece, or ... */
+    int *counts, *disps;  /* ... the caller's arrays (instances; counts NULL: `count`) */
+} move_side_t;
+
+typedef struct {
+    enum move_kind kind;
+    int root;        /* the rooted calls */
+    int bad;         /* an argument the engine does not take: the previous owner's to answer */
+    int no_prev;     /* a nonblocking slot nobody held before: no previous owner to go to */
+    int inplace;     /* MPI_IN_PLACE: the send side (scatter(v): the receive side) is not significant */
+    move_side_t s, r;  /* MOVE_BCAST: the one buffer as both, significant as s on the root, as r elsewhere */
+} movement_t;
+
+/* this rank's buffers are all device memory */
+static int move_dev(const movement_t *d)
+{
+    return (!d->s.sig || is_dev(d->s.buf)) && (!d->r.sig || is_dev(d->r.buf));
+}
+
+/* bytes a side spans from its true lower bound; SIZE_MAX: a negative displacement */
+static size_t move_span(const move_side_t *x)
+{
+    return x->counts ? vspan(x->dt, x->n, x->counts, x->disps) : dt_span(x->dt, (size_t)x->count * (size_t)x->n);
+}
+
+/* the previous owner's call on (s, r); request NULL: blocking, else the post (allgather and bcast) */
+static int movement_prev(mca_coll_mi355x_module_t *m, const movement_t *d, void *s, void *r, struct ompi_communicator_t *comm,
+                         ompi_request_t **request)
+{
+    const move_side_t *x = &d->s, *y = &d->r;
+    if (d->no_prev) return OMPI_ERR_NOT_SUPPORTED;
+    switch (d->kind) {
+    case MOVE_ALLGATHER:
+        return request ? m->prev_iallgather(s, x->count, x->dt, r, y->count, y->dt, comm, request, m->prev_iallgather_module)
+                       : m->prev_allgather(s, x->count, x->dt, r, y->count, y->dt, comm, m->prev_allgather_module);
+    case MOVE_BCAST:
+        return request ? m->prev_ibcast(x->sig ? s : r, x->count, x->dt, d->root, comm, request, m->prev_ibcast_module)
+                       : m->prev_bcast(x->sig ? s : r, x->count, x->dt, d->root, comm, m->prev_bcast_module);
+    case MOVE_GATHER:
+        return m->prev_gather(s, x->count, x->dt, r, y->count, y->dt, d->root, comm, m->prev_gather_module);
+    case MOVE_GATHERV:
+        return m->prev_gatherv(s, x->count, x->dt, r, y->counts, y->disps, y->dt, d->root, comm, m->prev_gatherv_module);
+    case MOVE_SCATTER:
+        return m->prev_scatter(s, x->count, x->dt, r, y->count, y->dt, d->root, comm, m->prev_scatter_module);
+    case MOVE_SCATTERV:
+        return m->prev_scatterv(s, x->counts, x->disps, x->dt, r, y->count, y->dt, d->root, comm, m->prev_scatterv_module);
+    case MOVE_ALLGATHERV:
+        return m->prev_allgatherv(s, x->count, x->dt, r, y->counts, y->disps, y->dt, comm, m->prev_allgatherv_module);
+    case MOVE_ALLTOALL:
+        return m->prev_alltoall(s, x->count, x->dt, r, y->count, y->dt, comm, m->prev_alltoall_module);
+    default:
+        return m->prev_alltoallv(s, x->counts, x->disps, x->dt, r, y->counts, y->disps, y->dt, comm,
+                                 m->prev_alltoallv_module);
+    }
+}
+
+/* The previous owner with this rank's significant device buffers staged through host memory (coll/cuda's
+ * rule applied to the movement calls): the send span is copied in and never back; the receive span is
+ * copied in too (its gaps keep their bytes) and back after a call that succeeded.  A negative displacement
+ * is an error, decided before anything is staged.  A nonblocking form stages at initiation and copies
+ * back when the host request completes (nb_staged_start). */
+static int movement_staged(mca_coll_mi355x_module_t *m, const movement_t *d, struct ompi_communicator_t *comm,
+                           ompi_request_t **request)
+{
+    if (d->no_prev) return OMPI_ERR_NOT_SUPPORTED;
+    const size_t ss = d->s.sig ? move_span(&d->s) : 0, rs = d->r.sig ? move_span(&d->r) : 0;
+    if (ss == (size_t)-1 || rs == (size_t)-1) return OMPI_ERR_NOT_SUPPORTED;
+    hstage_t st[2];
+    void *s = d->s.buf, *r = d->r.buf;
+    int rc = hstage2(st, d->s.sig ? &s : NULL, d->s.dt, ss, d->r.sig ? &r : NULL, d->r.dt, rs, 1, rs);
+    if (rc != OMPI_SUCCESS) return rc;
+    if (!request) return hunstage2(st, movement_prev(m, d, s, r, comm, NULL));
+    ompi_request_t *inner = NULL;
+    rc = movement_prev(m, d, s, r, comm, &inner);
+    return nb_staged_start(comm, request, st, inner, rc);
+}
+
+/* The engine step of every call but allgather and bcast: the significant sides set up (scratch slot 0:
+ * send, 1: receive), what this rank sends packed -- its send side whole; in place the receive side's piece
+ * `me` (gather(v), allgatherv) or every piece (alltoall(v)) -- the engine's call, the receive side unpacked. */
+static int sides_engine(mca_coll_mi355x_module_t *m, const movement_t *d, struct ompi_communicator_t *comm)
+{
+    const int me = mi355x_comm_rank_of(comm), root = d->root, ssig = d->s.sig, rsig = d->r.sig;
+    const int every = d->kind == MOVE_ALLTOALL || d->kind == MOVE_ALLTOALLV;
+    side_t snd, rcv;
+    int rc = OMPI_SUCCESS;
+    if (ssig && (rc = side_init(m, &snd, 0, d->s.buf, d->s.dt, d->s.n, d->s.counts, d->s.count, d->s.disps))) return rc;
+    if (rsig && (rc = side_init(m, &rcv, 1, d->r.buf, d->r.dt, d->r.n, d->r.counts, d->r.count, d->r.disps))) return rc;
+    if (d->kind == MOVE_ALLTOALL && ssig && snd.bytes[0] != rcv.bytes[0]) return OMPI_ERR_BAD_PARAM;
+    int erc = ssig ? side_move(m, &snd, -1, 1) : d->inplace ? side_move(m, &rcv, every ? -1 : me, 1) : MI355X_SUCCESS;
+    if (erc != MI355X_SUCCESS) return map_rc(erc);
+    mi355x_comm_t *e = m->engine;
+    const void *sv = ssig ? snd.view : NULL;
+    void *rv = rsig ? rcv.view : NULL;
+    const size_t *sbytes = ssig ? snd.bytes : NULL, *soff = ssig ? snd.off : NULL;
+    const size_t *rbytes = rsig ? rcv.bytes : NULL, *roff = rsig ? rcv.off : NULL;
+    switch (d->kind) {
+    case MOVE_GATHER: erc = mi355x_gather(e, sv, rv, ssig ? sbytes[0] : rbytes[me], root, NULL); break;
+    case MOVE_GATHERV: erc = mi355x_gatherv(e, sv, ssig ? sbytes[0] : 0, rv, rbytes, roff, root, NULL); break;
+    case MOVE_SCATTER: erc = mi355x_scatter(e, sv, rv, ssig ? sbytes[0] : rbytes[0], root, NULL); break;
+    case MOVE_SCATTERV: erc = mi355x_scatterv(e, sv, sbytes, soff, rv, rsig ? rbytes[0] : 0, root, NULL); break;
+    case MOVE_ALLGATHERV: erc = mi355x_allgatherv(e, sv, ssig ? sbytes[0] : 0, rv, rbytes, roff, NULL); break;
+    case MOVE_ALLTOALL: erc = mi355x_alltoall(e, sv, rv, rbytes[0], NULL); break;
+    default: erc = mi355x_alltoallv(e, sv, sbytes, soff, rv, rbytes, roff, NULL); break;
+    }
+    if (erc == MI355X_SUCCESS && rsig && (rcv.d || rcv.host)) {
+        erc = side_move(m, &rcv, -1, 0);
+        if (erc == MI355X_SUCCESS) erc = mi355x_stream_sync(NULL);
+    }
+    return map_rc(erc);
+}
+
+/* Every rank votes its buffer kind (route): a call whose ranks all hold host buffers runs in the
+ * previous owner, a device rank of it staged; otherwise it runs in the engine.  The vote is collective:
+ * it is taken once per call, before any return that depends on a rank-local layout. */
+static int movement_blocking(mca_coll_mi355x_module_t *m, const movement_t *d, struct ompi_communicator_t *comm)
+{
+    if (d->bad) return movement_prev(m, d, d->s.buf, d->r.buf, comm, NULL);
+    const int dev = move_dev(d);
+    const int engine = route(m, dev);
+    if (engine < 0) return OMPI_ERROR;
+    if (engine == 0) return dev ? movement_staged(m, d, comm, NULL) : movement_prev(m, d, d->s.buf, d->r.buf, comm, NULL);
+    switch (d->kind) {
+    case MOVE_ALLGATHER:
+        return allgather_engine(m, dev, d->s.buf, d->s.count, d->s.dt, d->r.buf, d->r.count, d->r.dt, comm);
+    case MOVE_BCAST: return bcast_engine(m, dev, d->r.buf, d->r.count, d->r.dt, d->root, comm);
+    default: return sides_engine(m, d, comm);
+    }
+}
+
+/* No vote (a nonblocking initiation may not wait for its peers, see reduction_nonblocking): every rank
+ * enters the engine, unless coll_mi355x_mixed_buffers = 0 and this rank has a host side. */
+static int movement_nonblocking(mca_coll_mi355x_module_t *m, const movement_t *d, struct ompi_communicator_t *comm,
+                                ompi_request_t **request)
+{
+    if (d->bad) return movement_prev(m, d, d->s.buf, d->r.buf, comm, request);
+    if (!move_dev(d) && !m->mixed) return movement_staged(m, d, comm, request);
+    if (d->kind == MOVE_BCAST) return ibcast_engine(m, d->r.buf, d->r.count, d->r.dt, d->root, comm, request);
+    return iallgather_engine(m, d->s.buf, d->s.count, d->s.dt, d->r.buf, d->r.count, d->r.dt, comm, request);
+}
+
+/* a side in the caller's arguments: one piece, or (per_rank) one per rank; counts NULL: `count` each */
+static move_side_t side(void *buf, struct ompi_datatype_t *dt, int per_rank, int count, int *counts, int *disps)
+{
+    return (move_side_t){.buf = buf, .dt = dt, .n = per_rank ? 0 : 1, .count = count, .counts = counts, .disps = disps};
+}
+
+/* The description of a call from its kind and the caller's sides; the rules are today's, once.
+ * Significant: bcast -- the buffer is the send side on the root, the receive side elsewhere; gather(v)
+ * -- the send side not in place, the receive side on the root; scatter(v) -- the send side on the root,
+ * the receive side not in place; the others -- the send side not in place, the receive side always.
+ * Bad: a negative count of allgather or bcast; MPI_IN_PLACE on a non-root; more ranks than SIDE_MAX
+ * for the vector forms and alltoall.  (gather and scatter do not test that: side_init refuses such a
+ * communicator after the vote.  Left as it is.) */
+static movement_t movement(enum move_kind kind, int root, move_side_t s, move_side_t r, struct ompi_communicator_t *comm)
+{
+    const int n = mi355x_comm_size_of(comm), top = mi355x_comm_rank_of(comm) == root;
+    const int scat = kind == MOVE_SCATTER || kind == MOVE_SCATTERV, gath = kind == MOVE_GATHER || kind == MOVE_GATHERV;
+    const int inplace = (scat ? r.buf : s.buf) == MPI_IN_PLACE;
+    movement_t d = {.kind = kind, .root = root, .inplace = inplace, .s = s, .r = r};
+    d.s.sig = (kind == MOVE_BCAST || scat) ? top : !inplace;
+    d.r.sig = kind == MOVE_BCAST ? !top : scat ? !inplace : gath ? top : 1;
+    if (!s.n) d.s.n = n;
+    if (!r.n) d.r.n = n;
+    if (kind == MOVE_ALLGATHER) d.bad = r.count < 0 || (!inplace && s.count < 0);
+    else if (kind == MOVE_BCAST) d.bad = s.count < 0;
+    else d.bad = ((scat || gath) && inplace && !top) || (n > SIDE_MAX && kind != MOVE_GATHER && kind != MOVE_SCATTER);
+    return d;
+}
+
+int mca_coll_mi355x_allgather(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
+                              struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
+                              mca_coll_base_module_t *module)
+{
+    const movement_t d = movement(MOVE_ALLGATHER, 0, side(sbuf, sdtype, 0, scount, NULL, NULL),
+                                  side(rbuf, rdtype, 1, rcount, NULL, NULL), comm);
+    return movement_blocking(MOD(module), &d, comm);
+}
+
+int mca_coll_mi355x_iallgather(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
+                               struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
+                               ompi_request_t **request, mca_coll_base_module_t *module)
+{
+    movement_t d = movement(MOVE_ALLGATHER, 0, side(sbuf, sdtype, 0, scount, NULL, NULL),
+                            side(rbuf, rdtype, 1, rcount, NULL, NULL), comm);
+    d.no_prev = !MOD(module)->prev_iallgather;
+    return movement_nonblocking(MOD(module), &d, comm, request);
+}
+
+int mca_coll_mi355x_bcast(void *buff, int count, struct ompi_datatype_t *datatype, int root,
+                          struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    const move_side_t b = side(buff, datatype, 0, count, NULL, NULL);
+    const movement_t d = movement(MOVE_BCAST, root, b, b, comm);
+    return movement_blocking(MOD(module), &d, comm);
+}
+
+int mca_coll_mi355x_ibcast(void *buff, int count, struct ompi_datatype_t *datatype, int root,
+                           struct ompi_communicator_t *comm, ompi_request_t **request, mca_coll_base_module_t *module)
+{
+    const move_side_t b = side(buff, datatype, 0, count, NULL, NULL);
+    movement_t d = movement(MOVE_BCAST, root, b, b, comm);
+    d.no_prev = !MOD(module)->prev_ibcast;
+    return movement_nonblocking(MOD(module), &d, comm, request);
+}
+
+int mca_coll_mi355x_gather(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
+                           struct ompi_datatype_t *rdtype, int root, struct ompi_communicator_t *comm,
+                           mca_coll_base_module_t *module)
+{
+    const movement_t d = movement(MOVE_GATHER, root, side(sbuf, sdtype, 0, scount, NULL, NULL),
+                                  side(rbuf, rdtype, 1, rcount, NULL, NULL), comm);
+    return movement_blocking(MOD(module), &d, comm);
+}
+
+int mca_coll_mi355x_gatherv(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int *rcounts,
+                            int *disps, struct ompi_datatype_t *rdtype, int root, struct ompi_communicator_t *comm,
+                            mca_coll_base_module_t *module)
+{
+    const movement_t d = movement(MOVE_GATHERV, root, side(sbuf, sdtype, 0, scount, NULL, NULL),
+                                  side(rbuf, rdtype, 1, 0, rcounts, disps), comm);
+    return movement_blocking(MOD(module), &d, comm);
+}
+
+int mca_coll_mi355x_scatter(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
+                            struct ompi_datatype_t *rdtype, int root, struct ompi_communicator_t *comm,
+                            mca_coll_base_module_t *module)
+{
+    const movement_t d = movement(MOVE_SCATTER, root, side(sbuf, sdtype, 1, scount, NULL, NULL),
+                                  side(rbuf, rdtype, 0, rcount, NULL, NULL), comm);
+    return movement_blocking(MOD(module), &d, comm);
+}
+
+int mca_coll_mi355x_scatterv(void *sbuf, int *scounts, int *disps, struct ompi_datatype_t *sdtype, void *rbuf,
+                             int rcount, struct ompi_datatype_t *rdtype, int root, struct ompi_communicator_t *comm,
+                             mca_coll_base_module_t *module)
+{
+    const movement_t d = movement(MOVE_SCATTERV, root, side(sbuf, sdtype, 1, 0, scounts, disps),
+                                  side(rbuf, rdtype, 0, rcount, NULL, NULL), comm);
+    return movement_blocking(MOD(module), &d, comm);
+}
+
+int mca_coll_mi355x_allgatherv(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int *rcounts,
+                               int *disps, struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
+                               mca_coll_base_module_t *module)
+{
+    const movement_t d = movement(MOVE_ALLGATHERV, 0, side(sbuf, sdtype, 0, scount, NULL, NULL),
+                                  side(rbuf, rdtype, 1, 0, rcounts, disps), comm);
+    return movement_blocking(MOD(module), &d, comm);
+}
+
+int mca_coll_mi355x_alltoall(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
+                             struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
+                             mca_coll_base_module_t *module)
+{
+    const movement_t d = movement(MOVE_ALLTOALL, 0, side(sbuf, sdtype, 1, scount, NULL, NULL),
+                                  side(rbuf, rdtype, 1, rcount, NULL, NULL), comm);
+    return movement_blocking(MOD(module), &d, comm);
+}
+
+int mca_coll_mi355x_alltoallv(void *sbuf, int *scounts, int *sdisps, struct ompi_datatype_t *sdtype, void *rbuf,
+                              int *rcounts, int *rdisps, struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
+                              mca_coll_base_module_t *module)
+{
+    const movement_t d = movement(MOVE_ALLTOALLV, 0, side(sbuf, sdtype, 1, 0, scounts, sdisps),
+                                  side(rbuf, rdtype, 1, 0, rcounts, rdisps), comm);
+    return movement_blocking(MOD(module), &d, comm);
 }
 
 /* ------------------------------------------------------------------ reductions
@@ -1247,7 +1370,7 @@ static int reduction_staged(mca_coll_mi355x_module_t *m, const reduction_t *d, s
     const size_t in = dt_span(d->dtype, d->in), out = dt_span(d->dtype, d->out);
     hstage_t st[2];
     void *s = d->sbuf, *r = d->rsig ? d->rbuf : NULL;
-    int rc = hstage2(st, &s, in, &r, d->inplace ? in : out, d->rfill, out, d->dtype);
+    int rc = hstage2(st, &s, d->dtype, in, &r, d->dtype, d->inplace ? in : out, d->rfill, out);
     if (rc != OMPI_SUCCESS) return rc;
     if (!request) return hunstage2(st, red_prev(m, d, s, d->rsig ? r : d->rbuf, comm, NULL));
     ompi_request_t *inner = NULL;
@@ -1505,138 +1628,6 @@ int mca_coll_mi355x_iexscan(void *sbuf, void *rbuf, int count, struct ompi_datat
     reduction_t d = red_scan(1, sbuf, rbuf, count, dtype, op);
     d.no_prev = !MOD(module)->prev_iexscan;
     return reduction_nonblocking(MOD(module), &d, comm, request);
-}
-
-/* ------------------------------------------------------------------ nonblocking movement */
-
-/* the (count, dt) side of a staged nonblocking move: pack it into `p` now (local work), or set up
- * the completion-time unpack into `st` (the request then owns a private layout of dt) */
-static int nb_stage_side(int pack, void *buf, size_t count, const struct ompi_datatype_t *dt, void *p, size_t bytes,
-                         struct nb_stage *st)
-{
-    size_t cb;
-    if (contiguous_bytes_n(dt, count, &cb)) {
-        if (pack) return mi355x_memcpy_async(p, buf, bytes, NULL);
-        st->ubuf = buf;
-        return MI355X_SUCCESS;
-    }
-    mi355x_ddt_t *d = ddt_private(dt);
-    if (!d) return MI355X_ERR_UNSUPPORTED;
-    if (pack) {
-        st->pd = d;  /* the pack kernel reads its run tables until it finishes: released at completion */
-        return mi355x_pack(d, count, buf, 0, p, bytes, NULL, NULL);
-    }
-    st->ubuf = buf;
-    st->ucount = count;
-    st->ud = d;
-    return MI355X_SUCCESS;
-}
-
-/* Contiguous layouts go straight to the engine.  Derived layouts -- on any rank, whatever the
- * others use (MPI lets layouts differ; only the type signatures match) -- also stay in the
- * engine: my block is packed into a per-request staging buffer at initiation, the engine gathers
- * the packed blocks in place, and the completion unpacks them into rbuf (all local work, so the
- * call stays nonblocking); rank-local fallbacks to libnbc would leave the ranks in different
- * components. */
-int mca_coll_mi355x_iallgather(void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
-                               struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
-                               ompi_request_t **request, mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    const int inplace = (sbuf == MPI_IN_PLACE);
-    size_t rb = 0, sb = 0;
-    if (rcount < 0 || (!inplace && scount < 0))
-        NB_FALLBACK(iallgather, sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, request);
-    const int rh = !is_dev(rbuf), sh = !inplace && !is_dev(sbuf);
-    if ((rh || sh) && !m->mixed) {  /* a host side, one kind per call: device sides staged to the host */
-        if (!m->prev_iallgather) return OMPI_ERR_NOT_SUPPORTED;
-        const size_t n = (size_t)mi355x_comm_size_of(comm);
-        hstage_t st[2];
-        int rc = hstage(&st[0], &sbuf, sdtype, inplace ? 0 : dt_span(sdtype, (size_t)scount), 1, 0);
-        if (rc != OMPI_SUCCESS) return rc;
-        const size_t rspan = dt_span(rdtype, (size_t)rcount * n);
-        if ((rc = hstage(&st[1], &rbuf, rdtype, rspan, inplace, rspan)) != OMPI_SUCCESS) return hunstage(&st[0], rc);
-        if (st[0].h || st[1].h) __atomic_add_fetch(&mca_coll_mi355x_staged_calls, 1, __ATOMIC_RELAXED);
-        ompi_request_t *inner = NULL;
-        rc = m->prev_iallgather(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, &inner, m->prev_iallgather_module);
-        return nb_staged_start(comm, request, st, inner, rc);
-    }
-    mi355x_request_t *eng = NULL;
-    if (!rh && !sh && contiguous_bytes(rdtype, rcount, &rb) &&
-        (inplace || (contiguous_bytes(sdtype, scount, &sb) && sb == rb))) {
-        int rc = mi355x_iallgather(m->engine, inplace ? NULL : sbuf, rbuf, rb, NULL, &eng);
-        return rc ? map_rc(rc) : nb_start(eng, comm, request, 0, NULL);
-    }
-    /* derived layouts or host sides (a host rank joins the engine, nb_host_join): my block packed
-     * into the per-request staging buffer now, the n blocks moved out of it at completion */
-    const int n = mi355x_comm_size_of(comm), me = mi355x_comm_rank_of(comm);
-    const size_t blk = (size_t)rcount * rdtype->super.size;
-    if (!inplace && (size_t)scount * sdtype->super.size != blk) return OMPI_ERR_BAD_PARAM;
-    struct nb_stage st = {NULL, blk * (size_t)n, NULL, 0, NULL, NULL, 0};
-    if (mi355x_malloc(&st.stage, st.bytes ? st.bytes : 1) != MI355X_SUCCESS) return OMPI_ERR_OUT_OF_RESOURCE;
-    const ptrdiff_t rext = rdtype->super.ub - rdtype->super.lb;
-    int rc;
-    if (inplace && rh)
-        rc = xstage(m, 1, (char *)rbuf + (ptrdiff_t)me * rcount * rext, rcount, rdtype, (char *)st.stage + blk * me, blk, 1);
-    else if (sh)
-        rc = xstage(m, 1, sbuf, scount, sdtype, (char *)st.stage + blk * me, blk, 1);
-    else
-        rc = inplace ? nb_stage_side(1, (char *)rbuf + (ptrdiff_t)me * rcount * rext, rcount, rdtype,
-                                     (char *)st.stage + blk * me, blk, &st)
-                     : nb_stage_side(1, sbuf, scount, sdtype, (char *)st.stage + blk * me, blk, &st);
-    if (rc == MI355X_SUCCESS && rh) {
-        st.ubuf = rbuf;
-        st.ucount = (size_t)rcount * (size_t)n;
-        st.uhost = 1;
-        if (!contiguous_bytes_n(rdtype, st.ucount, &rb) && !(st.ud = ddt_private(rdtype))) rc = MI355X_ERR_UNSUPPORTED;
-    } else if (rc == MI355X_SUCCESS) {
-        rc = nb_stage_side(0, rbuf, (size_t)rcount * (size_t)n, rdtype, st.stage, st.bytes, &st);
-    }
-    if (rc == MI355X_SUCCESS) rc = mi355x_iallgather(m->engine, NULL, st.stage, blk, NULL, &eng);
-    if (rc != MI355X_SUCCESS) {
-        if (rc == MI355X_ERR_UNSUPPORTED)
-            fprintf(stderr, "[coll/mi355x] iallgather: the GPU convertor cannot describe the datatype\n");
-        nb_stage_release(&st);
-        return map_rc(rc);
-    }
-    return nb_start(eng, comm, request, 0, &st);
-}
-
-/* derived layouts as in iallgather: the root packs at initiation, the others unpack at completion */
-int mca_coll_mi355x_ibcast(void *buff, int count, struct ompi_datatype_t *datatype, int root,
-                           struct ompi_communicator_t *comm, ompi_request_t **request, mca_coll_base_module_t *module)
-{
-    mca_coll_mi355x_module_t *m = MOD(module);
-    size_t bytes = 0;
-    const int host = !is_dev(buff);
-    if (count < 0 || (host && !m->mixed)) NB_FALLBACK(ibcast, buff, count, datatype, root, comm, request);
-    mi355x_request_t *eng = NULL;
-    if (!host && contiguous_bytes(datatype, count, &bytes)) {
-        int rc = mi355x_ibcast(m->engine, buff, bytes, root, NULL, &eng);
-        return rc ? map_rc(rc) : nb_start(eng, comm, request, 0, NULL);
-    }
-    const int me = mi355x_comm_rank_of(comm);
-    struct nb_stage st = {NULL, (size_t)count * datatype->super.size, NULL, 0, NULL, NULL, 0};
-    if (mi355x_malloc(&st.stage, st.bytes ? st.bytes : 1) != MI355X_SUCCESS) return OMPI_ERR_OUT_OF_RESOURCE;
-    int rc = MI355X_SUCCESS;
-    if (!host) {
-        rc = nb_stage_side(me == root, buff, count, datatype, st.stage, st.bytes, &st);
-    } else if (me == root) {  /* a host rank joining the engine (nb_host_join): packed / copied now */
-        rc = xstage(m, 1, buff, (size_t)count, datatype, st.stage, st.bytes, 1);
-    } else {                  /* ... or moved out of the staging buffer at completion */
-        st.ubuf = buff;
-        st.ucount = (size_t)count;
-        st.uhost = 1;
-        if (!contiguous_bytes(datatype, count, &bytes) && !(st.ud = ddt_private(datatype))) rc = MI355X_ERR_UNSUPPORTED;
-    }
-    if (rc == MI355X_SUCCESS) rc = mi355x_ibcast(m->engine, st.stage, st.bytes, root, NULL, &eng);
-    if (rc != MI355X_SUCCESS) {
-        if (rc == MI355X_ERR_UNSUPPORTED)
-            fprintf(stderr, "[coll/mi355x] ibcast: the GPU convertor cannot describe datatype %s\n", datatype->name);
-        nb_stage_release(&st);
-        return map_rc(rc);
-    }
-    return nb_start(eng, comm, request, 0, &st);
 }
 
 /* ------------------------------------------------------------------ point-to-point (PML hook)
