@@ -198,17 +198,33 @@ def test_x87_arith_slots(gpu, pkg, oracle, tname):
                                    g[bad[:2]].tolist(), w[bad[:2]].tolist())
 
 
-@pytest.mark.parametrize("offs", [(0, 0, 0), (1, 1, 1), (1, 0, 2)], ids=["aligned", "comisaligned", "misaligned"])
+@pytest.mark.parametrize("offs", [(0, 0, 0), (1, 1, 1), (1, 0, 2), ("align", 1, 1, 1), ("align", 1, 0, 3)],
+                         ids=["aligned", "comisaligned", "misaligned", "align_comisaligned", "align_misaligned"])
 def test_all_slots(gpu, pkg, oracle, offs):
+    """offs: the operands' offsets in elements; ("align", ...): in units of the type's C alignment
+    where that is smaller than its size (the pairs: FLOAT_INT is 8 bytes with 4-byte alignment; the
+    complex types), so a legal buffer sits at 4 mod 8, 8 mod 16 or 16 mod 32 -- a multiple of the
+    alignment that is no multiple of the size.  Co-misaligned: every operand one unit off; mutually:
+    one, none and three units (for a 16-byte type with 8-byte alignment 8 is the only such residue
+    mod 16, so the operand that differs from it is aligned)."""
     torch = gpu
     bad = []
+    by_alignment = offs[0] == "align"
+    ran = 0
     for opname, tname in _slots(pkg, oracle):
         op, ty = pkg.OP[opname], pkg.T[tname]
         esz = pkg.type_size(ty)
         assert esz == oracle.oracle_type_size(ty)
+        unit = esz
+        if by_alignment:
+            unit = opdata.dtype_of(tname).alignment
+            if unit == esz:
+                continue
+            assert unit < esz and (3 * unit) % esz != 0
+        ran += 1
         a = opdata.make(tname, N, 1)
         b = opdata.make(tname, N, 2)
-        o1, o2, o3 = (x * esz for x in offs)
+        o1, o2, o3 = (x * unit for x in offs[-3:])
         # 3-buff
         ta, pa = _dev(torch, a, o1)
         tb, pb = _dev(torch, b, o2)
@@ -232,6 +248,8 @@ def test_all_slots(gpu, pkg, oracle, offs):
         except AssertionError as e:
             bad.append(str(e))
     assert not bad, "\n".join(bad[:20])
+    # the six pair types x MAXLOC / MINLOC and the three complex types x SUM / PROD
+    assert ran == (18 if by_alignment else len(_slots(pkg, oracle)))
 
 
 @pytest.mark.parametrize("offs", [(0, 0, 0), (32, 48, 16), (8, 8, 8), (0, 8, 0)],

@@ -21,7 +21,7 @@ import nbc_scan_oracle as nbs
 import opdata
 from mini import mini
 
-SIZES = list(range(1, 10))
+SIZES = list(range(1, 10)) + [10, 16, 17, 33]   # 10: the first size whose exclusive form holds a store back
 
 
 def _counts(n):

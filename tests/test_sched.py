@@ -48,9 +48,14 @@ def eval_program(oracle, prog, op, ty, xs):
 CASES = [("SUM", "FLOAT"), ("MAX", "DOUBLE"), ("MAXLOC", "FLOAT_INT"), ("PROD", "C_FLOAT_COMPLEX")]
 
 
-@pytest.mark.parametrize("n", [2, 3, 4, 5, 6, 7, 8, 11, 16])
+@pytest.mark.parametrize("n", [2, 3, 4, 5, 6, 7, 8, 11, 16, 17, 33, 64])
 @pytest.mark.parametrize("alg", [3, 4, 5])
 def test_allreduce_programs(pkg, oracle, n, alg):
+    """past 16 ranks (kTreeMax) the ring blocks stay exact folds and recursive doubling is refused"""
+    if alg == 3 and n > 16:
+        with pytest.raises(pkg.MI355XError, match="MI355X_ERR_UNSUPPORTED"):
+            pkg.sched_program(1, n, 3, 0)
+        return
     count = 37 * n + 5 if alg != 3 else 257   # ring: uneven early/late blocks
     for opname, tname in CASES:
         op, ty = pkg.OP[opname], pkg.T[tname]
@@ -82,9 +87,16 @@ def _ring_block(count, n, b):
     return off, (early if b < split else late)
 
 
-@pytest.mark.parametrize("n", [2, 3, 4, 5, 7, 8, 13])
+@pytest.mark.parametrize("n", [2, 3, 4, 5, 7, 8, 13, 17, 33, 64])
 @pytest.mark.parametrize("ralg", [1, 2, 3, 4, 5])
 def test_reduce_programs(pkg, oracle, n, ralg):
+    """past 16 ranks (kTreeMax) linear (1) and pipeline (3) stay exact folds; the chain with its
+    default fan-out (2), binary (4) and binomial (5) are trees and are refused"""
+    if n > 16 and ralg in (2, 4, 5):
+        for root in sorted({0, n // 2, n - 1}):
+            with pytest.raises(pkg.MI355XError, match="MI355X_ERR_UNSUPPORTED"):
+                pkg.sched_program(2, n, ralg, root)
+        return
     count = 101
     for opname, tname in CASES:
         op, ty = pkg.OP[opname], pkg.T[tname]
@@ -108,6 +120,35 @@ def test_reduce_chain_fanouts(pkg, oracle, n, fanout):
                                    want.ctypes.data) == 2
     got = eval_program(oracle, pkg.sched_program(5, n, 0, fanout), pkg.OP["SUM"], pkg.T["FLOAT"], xs)
     opdata.assert_same("FLOAT", "SUM", got, want, f"chain n={n} fanout={fanout}")
+
+
+@pytest.mark.parametrize("n", [17, 33, 64])
+def test_fold_programs_past_16_ranks(pkg, oracle, n):
+    """the other fold forms past kTreeMax: the reduce_scatter ring blocks (a zero count among them)
+    and the chain with fan-out 1 are exact against the oracle; recursive halving and a chain with
+    two branches are trees and are refused"""
+    rng = np.random.default_rng(n)
+    rcounts = [int(v) for v in rng.integers(0, 9, n)]
+    rcounts[0], rcounts[n // 2] = max(rcounts[0], 1), 0
+    disp = np.concatenate([[0], np.cumsum(rcounts)])
+    rc = (ctypes.c_int * n)(*rcounts)
+    for opname, tname in CASES:
+        op, ty = pkg.OP[opname], pkg.T[tname]
+        xs = [opdata.make(tname, int(disp[-1]), 50 + r) for r in range(n)]
+        outs = [np.zeros(max(c, 1), dtype=xs[0].dtype) for c in rcounts]
+        assert oracle.oracle_reduce_scatter_alg(3, n, rc, ty, op, _ptrs(xs), _ptrs(outs)) == 3
+        for b in range(n):
+            lo, hi = disp[b], disp[b + 1]
+            got = eval_program(oracle, pkg.sched_program(3, n, 0, b), op, ty, [x[lo:hi] for x in xs])
+            opdata.assert_same(tname, opname, got, outs[b][:rcounts[b]], f"rs ring n={n} b={b}")
+        xs = [opdata.make(tname, 64, 60 + r) for r in range(n)]
+        want = np.zeros_like(xs[0])
+        assert oracle.oracle_reduce_fo(2, n, 0, 1, 64, ty, op, _ptrs(xs), want.ctypes.data) == 2
+        got = eval_program(oracle, pkg.sched_program(5, n, 0, 1), op, ty, xs)
+        opdata.assert_same(tname, opname, got, want, f"chain n={n} fan-out 1")
+    for kind, block in ((4, 0), (5, 2)):
+        with pytest.raises(pkg.MI355XError, match="MI355X_ERR_UNSUPPORTED"):
+            pkg.sched_program(kind, n, 0, block)
 
 
 def test_chain_fanout_changes_the_order(pkg, oracle):
