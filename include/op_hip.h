@@ -15,8 +15,12 @@
  *                                          slot before op/hip (op/base's CPU loop), unchanged;
  *   - any operand in device memory      -> HIP kernel on the null stream, then stream sync; a
  *                                          host operand is staged through device scratch;
- *   - x87 long double slots on device   -> staged to the host and run by the lower-priority
- *                                          function (CDNA4 has no 80-bit format);
+ *   - x87 long double slots on device   -> HIP kernels as every other slot: MAX / MIN / MAXLOC /
+ *                                          MINLOC compare and select on the 80-bit encoding,
+ *                                          SUM / PROD run the x87 add / multiply in integer
+ *                                          arithmetic (CDNA4 has no 80-bit format); staging to
+ *                                          the host remains only for a runtime that reports such
+ *                                          a slot unsupported;
  *   - a HIP failure                     -> abort(), as opal_cuda_memcpy does
  *                                          (opal/datatype/opal_datatype_cuda.c:106-111); the
  *                                          op ABI has no error return (op.h:519-520).

@@ -23,100 +23,29 @@
 // Source/destination pointers arrive in the kernarg segment (uniform, scalar-loaded), so the
 // per-rank indirection costs no VGPRs.  Same alignment scheme as op_kernels.hip: if every
 // pointer shares the misalignment mod 16 a scalar head peels to the 16-B body, else the whole
-// range runs element-wise.
+// range runs element-wise.  The split, the vector access, the ordered fold (load_chunk /
+// fold_chunk / store_vecs) and the launch plumbing are stream_core.hpp's, shared with
+// op_kernels.hip and coll_pipe.hip.
 #include "coll_internal.hpp"
 #include "op_functors.hpp"
 #include "rt_internal.hpp"
 #include "slot_list.hpp"
+#include "stream_core.hpp"
 
 namespace mi355x {
 
-typedef unsigned int u32x4c __attribute__((ext_vector_type(4)));
-
-template <typename T> struct alignas(16) CVec {
-    T e[16 / sizeof(T)];
-};
-
-template <typename V> __device__ __forceinline__ V cload(const void *p)
-{
-    u32x4c raw = *reinterpret_cast<const u32x4c *>(p);
-    V v;
-    __builtin_memcpy(&v, &raw, 16);
-    return v;
-}
-template <typename V> __device__ __forceinline__ void cstore(void *p, const V &v)
-{
-    u32x4c raw;
-    __builtin_memcpy(&raw, &v, 16);
-    *reinterpret_cast<u32x4c *>(p) = raw;
-}
-// non-temporal forms: streams larger than the Infinity Cache (same policy as op_kernels.hip)
-template <bool NT, typename V> __device__ __forceinline__ V cload_t(const void *p)
-{
-    if constexpr (!NT) return cload<V>(p);
-    u32x4c raw = __builtin_nontemporal_load(reinterpret_cast<const u32x4c *>(p));
-    V v;
-    __builtin_memcpy(&v, &raw, 16);
-    return v;
-}
-template <bool NT, typename V> __device__ __forceinline__ void cstore_t(void *p, const V &v)
-{
-    if constexpr (!NT) {
-        cstore<V>(p, v);
-    } else {
-        u32x4c raw;
-        __builtin_memcpy(&raw, &v, 16);
-        __builtin_nontemporal_store(raw, reinterpret_cast<u32x4c *>(p));
-    }
-}
-
-// ------------------------------------------------------------------ the two reduction rules
-// THREE: the 3-buff rule op3(in1 = o, in2 = a) of coll/libnbc's programs (Program::three) instead
-// of the 2-buff rule op2(out = o, in = a).  The two differ for the MAXLOC / MINLOC pairs only
-// (op_functors.hpp: a NaN value, the value kept on a tie), so only those slots instantiate the
-// THREE kernels; every other slot's op3 is its op2 and a `three` program runs the op2 kernels.
-template <class F> struct Op3Differs : std::false_type {};
-template <typename P, bool MAX> struct Op3Differs<OpLoc<P, MAX>> : std::true_type {};
-
-template <class F, bool THREE>
-__device__ __forceinline__ typename F::T rule(const typename F::T &o, const typename F::T &a)
-{
-    if constexpr (THREE) return F::op3(o, a);
-    else return F::op2(o, a);
-}
-
 // ------------------------------------------------------------------ fold
-template <class F, bool THREE>
-__device__ __forceinline__ typename F::T fold_step(const typename F::T &acc, const typename F::T &x,
-                                                   bool acc_is_out)
-{
-    return acc_is_out ? rule<F, THREE>(acc, x) : rule<F, THREE>(x, acc);
-}
-
-// fold of element i (scalar path)
-template <class F, bool THREE>
-__device__ __forceinline__ typename F::T fold_scalar(const FoldArgs &a, size_t i)
-{
-    using T = typename F::T;
-    T acc = static_cast<const T *>(a.src[a.order[0]])[i];
-    for (int j = 1; j < a.nr; ++j) {
-        const T x = static_cast<const T *>(a.src[a.order[j]])[i];
-        acc = fold_step<F, THREE>(acc, x, (a.role_mask >> j) & 1u);
-    }
-    return acc;
-}
-
 template <class F, int U, bool NT, bool THREE>
 __global__ __launch_bounds__(256) void k_fold(FoldArgs a)
 {
     using T = typename F::T;
-    using V = CVec<T>;
+    using V = Vec16<T>;
     constexpr int EPV = 16 / sizeof(T);
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t nthr = (size_t)gridDim.x * blockDim.x;
 
     for (size_t i = tid; i < a.head; i += nthr) {
-        const T r = fold_scalar<F, THREE>(a, i);
+        const T r = fold_scalar<F, THREE>(a.src, a.order, a.role_mask, a.nr, i);
         for (int d = 0; d < a.nd; ++d) static_cast<T *>(a.dst[d])[i] = r;
     }
 
@@ -124,71 +53,25 @@ __global__ __launch_bounds__(256) void k_fold(FoldArgs a)
     const size_t hb = a.head * sizeof(T);
     for (size_t base = tid; base < nvec; base += nthr * U) {
         V acc[U];
-        // first chunk of up to 8 ranks: issue every load, then fold
+        // up to 8 ranks at a time: issue every load, then fold; the chunks keep the order.  The
+        // first chunk stays peeled: as one loop the kernel needs fewer registers, but nine ranks
+        // sharing a GPU ran 256 MiB per rank 1.5x slower (profiles/stream_core_speed.json)
         {
             V x[kFoldChunk][U];
-#pragma unroll
-            for (int j = 0; j < kFoldChunk; ++j) {
-                if (j < a.nr) {
-                    const char *p = static_cast<const char *>(a.src[a.order[j]]) + hb;
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const size_t v = base + (size_t)u * nthr;
-                        if (v < nvec) x[j][u] = cload_t<NT, V>(p + v * 16);
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc[u] = x[0][u];
-#pragma unroll
-            for (int j = 1; j < kFoldChunk; ++j) {
-                if (j < a.nr) {
-                    const bool ao = (a.role_mask >> j) & 1u;
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-#pragma unroll
-                        for (int e = 0; e < EPV; ++e) acc[u].e[e] = fold_step<F, THREE>(acc[u].e[e], x[j][u].e[e], ao);
-                }
-            }
+            load_chunk<NT, V>(x, a.src, a.order, hb, 0, a.nr, base, nthr, nvec);
+            fold_chunk<F, THREE>(acc, x, 0, a.nr, a.role_mask);
         }
-        // remaining ranks (communicators larger than 8), chunk by chunk, order preserved
         for (int j0 = kFoldChunk; j0 < a.nr; j0 += kFoldChunk) {
             V x[kFoldChunk][U];
-#pragma unroll
-            for (int j = 0; j < kFoldChunk; ++j) {
-                if (j0 + j < a.nr) {
-                    const char *p = static_cast<const char *>(a.src[a.order[j0 + j]]) + hb;
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const size_t v = base + (size_t)u * nthr;
-                        if (v < nvec) x[j][u] = cload_t<NT, V>(p + v * 16);
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < kFoldChunk; ++j) {
-                if (j0 + j < a.nr) {
-                    const bool ao = (a.role_mask >> (j0 + j)) & 1u;
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-#pragma unroll
-                        for (int e = 0; e < EPV; ++e) acc[u].e[e] = fold_step<F, THREE>(acc[u].e[e], x[j][u].e[e], ao);
-                }
-            }
+            load_chunk<NT, V>(x, a.src, a.order, hb, j0, a.nr, base, nthr, nvec);
+            fold_chunk<F, THREE>(acc, x, j0, a.nr, a.role_mask);
         }
-        for (int d = 0; d < a.nd; ++d) {
-            char *q = static_cast<char *>(a.dst[d]) + hb;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const size_t v = base + (size_t)u * nthr;
-                if (v < nvec) cstore_t<NT, V>(q + v * 16, acc[u]);
-            }
-        }
+        for (int d = 0; d < a.nd; ++d) store_vecs<NT>(static_cast<char *>(a.dst[d]) + hb, acc, base, nthr, nvec);
     }
 
     const size_t t0 = a.head + nvec * EPV;
     for (size_t i = t0 + tid; i < a.n; i += nthr) {
-        const T r = fold_scalar<F, THREE>(a, i);
+        const T r = fold_scalar<F, THREE>(a.src, a.order, a.role_mask, a.nr, i);
         for (int d = 0; d < a.nd; ++d) static_cast<T *>(a.dst[d])[i] = r;
     }
 }
@@ -221,7 +104,7 @@ template <class F, int U, bool NT, bool THREE>
 __global__ __launch_bounds__(256) void k_scan_part(ScanArgs a)
 {
     using T = typename F::T;
-    using V = CVec<T>;
+    using V = Vec16<T>;
     constexpr int EPV = 16 / sizeof(T);
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t nthr = (size_t)gridDim.x * blockDim.x;
@@ -238,24 +121,9 @@ __global__ __launch_bounds__(256) void k_scan_part(ScanArgs a)
         int pend = -1;  // destination whose store waits for the next chunk's loads
         for (int j0 = 0; j0 < nl; j0 += kFoldChunk) {
             V x[kFoldChunk][U];
-#pragma unroll
-            for (int j = 0; j < kFoldChunk; ++j) {
-                if (j0 + j < nl) {
-                    const char *p = static_cast<const char *>(a.src[j0 + j]) + hb;
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const size_t v = base + (size_t)u * nthr;
-                        if (v < nvec) x[j][u] = cload_t<NT, V>(p + v * 16);
-                    }
-                }
-            }
+            load_chunk<NT, V>(x, a.src, nullptr, hb, j0, nl, base, nthr, nvec);
             if (pend >= 0) {
-                char *q = static_cast<char *>(a.dst[pend]) + hb;
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const size_t v = base + (size_t)u * nthr;
-                    if (v < nvec) cstore_t<NT, V>(q + v * 16, acc[u]);
-                }
+                store_vecs<NT>(static_cast<char *>(a.dst[pend]) + hb, acc, base, nthr, nvec);
                 pend = -1;
             }
 #pragma unroll
@@ -274,12 +142,7 @@ __global__ __launch_bounds__(256) void k_scan_part(ScanArgs a)
                     // exclusive: x_{k+1} is loaded when it shares this chunk; when there is none
                     // (k + 1 == nl) the destination aliases no input that is read
                     if (!ex || j + 1 < kFoldChunk || k + 1 >= nl) {
-                        char *q = static_cast<char *>(a.dst[k + ex]) + hb;
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const size_t v = base + (size_t)u * nthr;
-                            if (v < nvec) cstore_t<NT, V>(q + v * 16, acc[u]);
-                        }
+                        store_vecs<NT>(static_cast<char *>(a.dst[k + ex]) + hb, acc, base, nthr, nvec);
                     } else {
                         pend = k + ex;
                     }
@@ -370,20 +233,9 @@ __global__ __launch_bounds__(256) void k_copy(CopyArgs a)
     const size_t nvec = a.nvec;
     constexpr int U = 4;
     for (size_t base = tid; base < nvec; base += nthr * U) {
-        u32x4c x[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t v = base + (size_t)u * nthr;
-            if (v < nvec) x[u] = *reinterpret_cast<const u32x4c *>(s + a.head + v * 16);
-        }
-        for (int d = 0; d < a.nd; ++d) {
-            char *q = static_cast<char *>(a.dst[d]) + a.head;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const size_t v = base + (size_t)u * nthr;
-                if (v < nvec) *reinterpret_cast<u32x4c *>(q + v * 16) = x[u];
-            }
-        }
+        u32x4 x[U];
+        load_vecs<false>(x, s + a.head, base, nthr, nvec);
+        for (int d = 0; d < a.nd; ++d) store_vecs<false>(static_cast<char *>(a.dst[d]) + a.head, x, base, nthr, nvec);
     }
     for (size_t i = a.head + nvec * 16 + tid; i < a.n; i += nthr)
         for (int d = 0; d < a.nd; ++d) static_cast<char *>(a.dst[d])[i] = s[i];
@@ -403,75 +255,38 @@ template <bool NT> __global__ __launch_bounds__(256) void k_multicopy(MultiCopyA
     const size_t tid = (size_t)b * blockDim.x + threadIdx.x;
     const size_t nthr = (size_t)nb * blockDim.x;
     const uintptr_t ms = (uintptr_t)s & 15, md = (uintptr_t)d & 15;
-    size_t head = n, nvec = 0;
-    if (ms == md) {
-        head = ms ? 16 - ms : 0;
-        if (head > n) head = n;
-        nvec = (n - head) / 16;
-    }
+    const Split16 sp = split16(n, 1, ms, ms == md);
+    const size_t head = sp.head, nvec = sp.nvec;
     for (size_t i = tid; i < head; i += nthr) d[i] = s[i];
     constexpr int U = 4;
     for (size_t base = tid; base < nvec; base += nthr * U) {
-        u32x4c x[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t v = base + (size_t)u * nthr;
-            if (v < nvec) x[u] = cload_t<NT, u32x4c>(s + head + v * 16);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t v = base + (size_t)u * nthr;
-            if (v < nvec) cstore_t<NT, u32x4c>(d + head + v * 16, x[u]);
-        }
+        u32x4 x[U];
+        load_vecs<NT>(x, s + head, base, nthr, nvec);
+        store_vecs<NT>(d + head, x, base, nthr, nvec);
     }
     for (size_t i = head + nvec * 16 + tid; i < n; i += nthr) d[i] = s[i];
 }
 
 // ------------------------------------------------------------------ launchers
-static size_t grid_for(size_t work, int blocks_per_cu)
-{
-    size_t blocks = (work + 255) / 256;
-    const size_t cap = (size_t)blocks_per_cu * (size_t)device_cu_count();
-    if (blocks > cap) blocks = cap;
-    return blocks ? blocks : 1;
-}
-
 template <class F> static int launch_fold(FoldArgs a, hipStream_t s)
 {
     using T = typename F::T;
     constexpr size_t EPV = 16 / sizeof(T);
     if (a.n == 0) return MI355X_SUCCESS;
-    uintptr_t m = (uintptr_t)a.src[a.order[0]] & 15;
-    bool co = (m % sizeof(T)) == 0;
-    for (int j = 0; j < a.nr && co; ++j) co = (((uintptr_t)a.src[j]) & 15) == m;
-    for (int d = 0; d < a.nd && co; ++d) co = (((uintptr_t)a.dst[d]) & 15) == m;
-    if (co) {
-        size_t head = m ? (16 - m) / sizeof(T) : 0;
-        if (head > a.n) head = a.n;
-        a.head = head;
-        a.nvec = (a.n - head) / EPV;
-    } else {
-        a.head = a.n;
-        a.nvec = 0;
-    }
+    // the pointers the kernel touches: the fold's first source, every source, every destination
+    const void *ptrs[1 + 2 * kMaxRanks];
+    int np = 0;
+    ptrs[np++] = a.src[a.order[0]];
+    for (int j = 0; j < a.nr; ++j) ptrs[np++] = a.src[j];
+    for (int d = 0; d < a.nd; ++d) ptrs[np++] = a.dst[d];
+    const Split16 sp = split16(a.n, sizeof(T), (uintptr_t)ptrs[0] & 15, co_aligned(sizeof(T), ptrs, np));
+    a.head = sp.head;
+    a.nvec = sp.nvec;
     constexpr int U = 2;
-    size_t work = a.nvec ? (a.nvec + U - 1) / U : 0;
-    const size_t scalar = a.n - a.nvec * EPV;
-    if (scalar > work) work = scalar;
-    const size_t blocks = grid_for(work, coll_tune().blocks_per_cu);
-    const bool nt = (size_t)(a.nr + a.nd) * a.n * sizeof(T) > ((size_t)256 << 20);
-    bool three = false;
-    if constexpr (Op3Differs<F>::value) three = a.three != 0;
-    if (three) {
-        if constexpr (Op3Differs<F>::value) {
-            if (nt) hipLaunchKernelGGL((k_fold<F, U, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_fold<F, U, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-        }
-    } else if (nt) {
-        hipLaunchKernelGGL((k_fold<F, U, true, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-    } else {
-        hipLaunchKernelGGL((k_fold<F, U, false, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-    }
+    const dim3 grid((unsigned)grid_for_split(sp, a.n, EPV, U, coll_tune().blocks_per_cu));
+    with_nt_three<F>(beyond_mall((size_t)(a.nr + a.nd) * a.n * sizeof(T)), a.three != 0, [&](auto nt, auto three) {
+        hipLaunchKernelGGL((k_fold<F, U, nt, three>), grid, dim3(256), 0, s, a);
+    });
     MI_HIP(hipGetLastError());
     return MI355X_SUCCESS;
 }
@@ -484,37 +299,18 @@ template <class F> static int launch_scan(ScanArgs a, hipStream_t s)
     if (a.n == 0 || nl <= 0) return MI355X_SUCCESS;
     if (a.nr > kMaxRanks) return set_error(MI355X_ERR_UNSUPPORTED, "scan over more than %d ranks", kMaxRanks);
     // the pointers the kernel touches: sources 0..nl-1, destinations ex..nr-1
-    const uintptr_t m = (uintptr_t)a.src[0] & 15;
-    bool co = (m % sizeof(T)) == 0;
-    for (int j = 0; j < nl && co; ++j) co = (((uintptr_t)a.src[j]) & 15) == m;
-    for (int d = ex; d < a.nr && co; ++d) co = (((uintptr_t)a.dst[d]) & 15) == m;
-    if (co) {
-        size_t head = m ? (16 - m) / sizeof(T) : 0;
-        if (head > a.n) head = a.n;
-        a.head = head;
-        a.nvec = (a.n - head) / EPV;
-    } else {
-        a.head = a.n;
-        a.nvec = 0;
-    }
+    const void *ptrs[2 * kMaxRanks];
+    int np = 0;
+    for (int j = 0; j < nl; ++j) ptrs[np++] = a.src[j];
+    for (int d = ex; d < a.nr; ++d) ptrs[np++] = a.dst[d];
+    const Split16 sp = split16(a.n, sizeof(T), (uintptr_t)ptrs[0] & 15, co_aligned(sizeof(T), ptrs, np));
+    a.head = sp.head;
+    a.nvec = sp.nvec;
     constexpr int U = 2;
-    size_t work = a.nvec ? (a.nvec + U - 1) / U : 0;
-    const size_t scalar = a.n - a.nvec * EPV;
-    if (scalar > work) work = scalar;
-    const size_t blocks = grid_for(work, coll_tune().blocks_per_cu);
-    const bool nt = (size_t)(2 * nl) * a.n * sizeof(T) > ((size_t)256 << 20);
-    bool three = false;
-    if constexpr (Op3Differs<F>::value) three = a.three != 0;
-    if (three) {
-        if constexpr (Op3Differs<F>::value) {
-            if (nt) hipLaunchKernelGGL((k_scan_part<F, U, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_scan_part<F, U, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-        }
-    } else if (nt) {
-        hipLaunchKernelGGL((k_scan_part<F, U, true, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-    } else {
-        hipLaunchKernelGGL((k_scan_part<F, U, false, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-    }
+    const dim3 grid((unsigned)grid_for_split(sp, a.n, EPV, U, coll_tune().blocks_per_cu));
+    with_nt_three<F>(beyond_mall((size_t)(2 * nl) * a.n * sizeof(T)), a.three != 0, [&](auto nt, auto three) {
+        hipLaunchKernelGGL((k_scan_part<F, U, nt, three>), grid, dim3(256), 0, s, a);
+    });
     MI_HIP(hipGetLastError());
     return MI355X_SUCCESS;
 }
@@ -536,14 +332,8 @@ template <class F> static int launch_ring_all(const RingAllArgs &a, hipStream_t 
 template <class F> static int launch_tree(const TreeArgs &a, hipStream_t s)
 {
     if (a.n == 0) return MI355X_SUCCESS;
-    const size_t blocks = grid_for(a.n, 4);
-    bool three = false;
-    if constexpr (Op3Differs<F>::value) three = a.three != 0;
-    if (three) {
-        if constexpr (Op3Differs<F>::value) hipLaunchKernelGGL((k_tree<F, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-    } else {
-        hipLaunchKernelGGL((k_tree<F, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-    }
+    const dim3 grid((unsigned)grid_for(a.n, 4));
+    with_three<F>(a.three != 0, [&](auto three) { hipLaunchKernelGGL((k_tree<F, three>), grid, dim3(256), 0, s, a); });
     MI_HIP(hipGetLastError());
     return MI355X_SUCCESS;
 }
@@ -551,20 +341,14 @@ template <class F> static int launch_tree(const TreeArgs &a, hipStream_t s)
 int launch_copy(CopyArgs a, hipStream_t s)
 {
     if (a.n == 0) return MI355X_SUCCESS;
-    uintptr_t m = (uintptr_t)a.src & 15;
-    bool co = true;
-    for (int d = 0; d < a.nd && co; ++d) co = (((uintptr_t)a.dst[d]) & 15) == m;
-    if (co) {
-        size_t head = m ? 16 - m : 0;
-        if (head > a.n) head = a.n;
-        a.head = head;
-        a.nvec = (a.n - head) / 16;
-    } else {
-        a.head = a.n;
-        a.nvec = 0;
-    }
-    size_t work = a.nvec ? (a.nvec + 3) / 4 : a.n;
-    const size_t blocks = grid_for(work, coll_tune().blocks_per_cu);
+    const void *ptrs[1 + kMaxRanks];
+    int np = 0;
+    ptrs[np++] = a.src;
+    for (int d = 0; d < a.nd; ++d) ptrs[np++] = a.dst[d];
+    const Split16 sp = split16(a.n, 1, (uintptr_t)a.src & 15, co_aligned(1, ptrs, np));
+    a.head = sp.head;
+    a.nvec = sp.nvec;
+    const size_t blocks = grid_for_split(sp, a.n, 16, 4, coll_tune().blocks_per_cu);  // k_copy's U
     hipLaunchKernelGGL(k_copy, dim3((unsigned)blocks), dim3(256), 0, s, a);
     MI_HIP(hipGetLastError());
     return MI355X_SUCCESS;
@@ -590,7 +374,7 @@ int launch_multicopy(MultiCopyArgs a, hipStream_t s)
     }
     a.first_block[a.nseg] = next;
     if (next == 0) return MI355X_SUCCESS;
-    if (2 * total > ((size_t)256 << 20))
+    if (beyond_mall(2 * total))
         hipLaunchKernelGGL(k_multicopy<true>, dim3(next), dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(k_multicopy<false>, dim3(next), dim3(256), 0, s, a);

@@ -7,10 +7,9 @@
 #include "coll_internal.hpp"
 #include "op_functors.hpp"
 #include "rt_internal.hpp"
+#include "stream_core.hpp"
 
 namespace mi355x {
-
-typedef unsigned int u32x4l __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint64_t ll_load(const uint64_t *p)
 {
@@ -29,7 +28,6 @@ __device__ __forceinline__ void ll_store(uint64_t *p, uint64_t v)
 // scalar with readfirstlane -- the service keeps its arguments in LDS, where the compiler cannot
 // see they are uniform; a per-lane base would compile to a loop over the wave's distinct values)
 // and each lane passes its own byte offset.
-constexpr int kLLSysCoherent = 1 | 16;  // gfx950 cache-policy bits: sc0 (1) | sc1 (16)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t ll_rsrc(const void *uniform_base)
 {
     const uint64_t u = (uint64_t)(uintptr_t)uniform_base;
@@ -47,25 +45,25 @@ __device__ __forceinline__ void ll_read16(const char *base, size_t off, size_t l
     if constexpr (SYS) {
         const __amdgpu_buffer_rsrc_t rs = ll_rsrc(base);
         if (len == 16 && (((uintptr_t)src) & 15) == 0) {
-            const u32x4l v = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)off, 0, kLLSysCoherent);
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)off, 0, kSysCoherent);
             w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
             return;
         }
         if ((((uintptr_t)src) & 3) == 0 && (len & 3) == 0) {  // whole words
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                w[i] = (size_t)(4 * i) < len ? __builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(off + 4 * i), 0, kLLSysCoherent) : 0;
+                w[i] = (size_t)(4 * i) < len ? __builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(off + 4 * i), 0, kSysCoherent) : 0;
             return;
         }
         unsigned char b[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i)
-            b[i] = (size_t)i < len ? __builtin_amdgcn_raw_buffer_load_b8(rs, (unsigned)(off + i), 0, kLLSysCoherent) : 0;
+            b[i] = (size_t)i < len ? __builtin_amdgcn_raw_buffer_load_b8(rs, (unsigned)(off + i), 0, kSysCoherent) : 0;
         __builtin_memcpy(w, b, 16);
         return;
     }
     if (len == 16 && (((uintptr_t)src) & 15) == 0) {
-        const u32x4l v = *reinterpret_cast<const u32x4l *>(src);
+        const u32x4 v = *reinterpret_cast<const u32x4 *>(src);
         w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
         return;
     }
@@ -81,14 +79,14 @@ __device__ __forceinline__ void ll_write16(char *base, size_t off, size_t len, c
     if constexpr (SYS) {
         const __amdgpu_buffer_rsrc_t rs = ll_rsrc(base);
         if (len == 16 && (((uintptr_t)dst) & 15) == 0) {
-            u32x4l v;
+            u32x4 v;
             v.x = w[0], v.y = w[1], v.z = w[2], v.w = w[3];
-            __builtin_amdgcn_raw_buffer_store_b128(v, rs, (unsigned)off, 0, kLLSysCoherent);
+            __builtin_amdgcn_raw_buffer_store_b128(v, rs, (unsigned)off, 0, kSysCoherent);
             return;
         }
         if ((((uintptr_t)dst) & 3) == 0 && (len & 3) == 0) {  // whole words (4- / 8-B elements)
             for (size_t i = 0; i < len / 4; ++i)
-                __builtin_amdgcn_raw_buffer_store_b32(w[i], rs, (unsigned)(off + 4 * i), 0, kLLSysCoherent);
+                __builtin_amdgcn_raw_buffer_store_b32(w[i], rs, (unsigned)(off + 4 * i), 0, kSysCoherent);
             return;
         }
         // (bytes taken from the words by shifts, unrolled: an indexed byte array would live in scratch)
@@ -96,13 +94,13 @@ __device__ __forceinline__ void ll_write16(char *base, size_t off, size_t len, c
         for (int i = 0; i < 16; ++i)
             if ((size_t)i < len)
                 __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(w[i >> 2] >> (8 * (i & 3))), rs, (unsigned)(off + i), 0,
-                                                     kLLSysCoherent);
+                                                     kSysCoherent);
         return;
     }
     if (len == 16 && (((uintptr_t)dst) & 15) == 0) {
-        u32x4l v;
+        u32x4 v;
         v.x = w[0], v.y = w[1], v.z = w[2], v.w = w[3];
-        *reinterpret_cast<u32x4l *>(dst) = v;
+        *reinterpret_cast<u32x4 *>(dst) = v;
         return;
     }
     unsigned char b[16];
@@ -178,8 +176,8 @@ __device__ __forceinline__ void ll_push_slice(const LLArgs &a, const LLBlock &k,
             // carries its own tag, so a store seen half-landed is only partly accepted
             const __amdgpu_buffer_rsrc_t rs = ll_rsrc(a.peer_data[q]);
             const unsigned o = (unsigned)(g0 * 8);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4l{w[0], k.tag, w[1], k.tag}, rs, o, 0, kLLSysCoherent);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4l{w[2], k.tag, w[3], k.tag}, rs, o + 16, 0, kLLSysCoherent);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{w[0], k.tag, w[1], k.tag}, rs, o, 0, kSysCoherent);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{w[2], k.tag, w[3], k.tag}, rs, o + 16, 0, kSysCoherent);
             continue;
         }
 #pragma unroll
@@ -207,8 +205,8 @@ static __device__ bool ll_recv(const LLArgs &a, const LLBlock &k, uint64_t qmask
     const int npair = (k.ngran + 1) / 2;  // pairs holding this thread's granules
     auto load_pair = [&](int q, int h) {
         // (a pair past ngran: the slot holds it, so the read stays inside the region)
-        const u32x4l v = __builtin_amdgcn_raw_buffer_load_b128(ll_rsrc(a.my_data + (size_t)q * a.slot_gran),
-                                                               (unsigned)(g0 * 8 + 16 * h), 0, kLLSysCoherent);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ll_rsrc(a.my_data + (size_t)q * a.slot_gran),
+                                                               (unsigned)(g0 * 8 + 16 * h), 0, kSysCoherent);
         w[q][2 * h] = v.x;
         w[q][2 * h + 1] = v.z;
         const bool lo = v.y == k.tag, hi = v.w == k.tag || 2 * h + 1 >= k.ngran;
@@ -253,10 +251,6 @@ static __device__ void ll_done(const LLArgs &a)
     for (int q = 0; q < a.n; ++q)
         if (q != a.me) ll_store(a.peer_ack[q], a.seq);
 }
-
-template <typename T> struct alignas(16) LLVec {
-    T e[16 / sizeof(T)];
-};
 
 // One element's value on every rank, indexed by rank at run time (tree programs, ring orders).
 // An array here ends up a dynamically indexed stack slot -- the compiler folds the select chains
@@ -330,7 +324,7 @@ template <class F, bool SYS = false>
 __device__ __forceinline__ void ll_reduce_out(const LLArgs &a, const LLBlock &k, const uint32_t (&w)[8][4])
 {
     using T = typename F::T;
-    using V = LLVec<T>;
+    using V = Vec16<T>;
     constexpr int EPV = 16 / sizeof(T);
     V xv[8];
 #pragma unroll

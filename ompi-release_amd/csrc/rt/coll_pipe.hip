@@ -25,54 +25,24 @@
 //     XCD's caches), then the workgroup copies the chunk with 16-B vectors.
 // Flags carry the call number and are compared with >=, so no reset between calls: a flag of
 // call s+1 can only be raised after every rank left call s (host barrier at the end of a call).
+// The fold of a chunk is k_fold's (load_chunk / fold_chunk, stream_core.hpp), with this file's own
+// write-through store; the splits and the vector access are the shared ones too.
 #include "coll_internal.hpp"
 #include "op_functors.hpp"
 #include "rt_internal.hpp"
 #include "slot_list.hpp"
+#include "stream_core.hpp"
 
 namespace mi355x {
-
-typedef unsigned int u32x4p __attribute__((ext_vector_type(4)));
-
-template <typename T> struct alignas(16) PVec {
-    T e[16 / sizeof(T)];
-};
-
-template <bool NT> __device__ __forceinline__ u32x4p pload(const void *p)
-{
-    if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x4p *>(p));
-    return *reinterpret_cast<const u32x4p *>(p);
-}
-template <bool NT> __device__ __forceinline__ void pstore(void *p, const u32x4p &v)
-{
-    if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4p *>(p));
-    else *reinterpret_cast<u32x4p *>(p) = v;
-}
 
 // write-through publishing (MI355X_KNOB_PIPE_WT): fold results stored with the system-coherent
 // cache policy (sc0 sc1: through the XCD's L2 to memory) and peers' results loaded the same way,
 // so a chunk needs neither the producer's L2 write-back fence nor the consumer's invalidate --
 // the hand-off form MI355X_MICROARCH.md measures faster for tens of KB per workgroup
 // ("publish-large").  Raw buffer ops carry the policy bits; the resource covers <= 2 GiB from base.
-constexpr int kSysCoherent = 1 | 16;  // gfx950 cache-policy bits: sc0 (1) | sc1 (16)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t wt_rsrc(const void *base)
 {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0x7fffffff, 0x00020000);
-}
-
-template <class F>
-__device__ __forceinline__ typename F::T pfold_step(const typename F::T &acc, const typename F::T &x, bool acc_is_out)
-{
-    return acc_is_out ? F::op2(acc, x) : F::op2(x, acc);
-}
-
-// element i (absolute index into the vector) folded in my block's order: scalar path
-template <class F> __device__ __forceinline__ typename F::T pfold_scalar(const PipeArgs &a, size_t i)
-{
-    using T = typename F::T;
-    T acc = static_cast<const T *>(a.src[a.order[0]])[i];
-    for (int j = 1; j < a.n; ++j) acc = pfold_step<F>(acc, static_cast<const T *>(a.src[a.order[j]])[i], (a.role_mask >> j) & 1u);
-    return acc;
 }
 
 // fold the vector body: U 16-B vectors per lane in flight per source, sources loaded FC at a time
@@ -80,7 +50,7 @@ template <class F, bool NT, int U, int FC>
 __device__ __forceinline__ void fold_body(const PipeArgs &a, typename F::T *dst, size_t v0, size_t nvec, bool wt)
 {
     using T = typename F::T;
-    using V = PVec<T>;
+    using V = Vec16<T>;
     constexpr int EPV = 16 / sizeof(T);
     const size_t t = threadIdx.x, nt = blockDim.x;
     const __amdgpu_buffer_rsrc_t rs = wt_rsrc(dst + v0);
@@ -88,43 +58,17 @@ __device__ __forceinline__ void fold_body(const PipeArgs &a, typename F::T *dst,
         V acc[U];
         for (int j0 = 0; j0 < a.n; j0 += FC) {
             V x[FC][U];
-#pragma unroll
-            for (int j = 0; j < FC; ++j) {
-                if (j0 + j < a.n) {
-                    const T *p = static_cast<const T *>(a.src[a.order[j0 + j]]) + v0;
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const size_t v = base + (size_t)u * nt;
-                        if (v < nvec) {
-                            const u32x4p raw = pload<NT>(p + v * EPV);
-                            __builtin_memcpy(&x[j][u], &raw, 16);
-                        }
-                    }
-                }
-            }
-            if (j0 == 0) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) acc[u] = x[0][u];
-            }
-#pragma unroll
-            for (int j = 0; j < FC; ++j) {
-                if (j0 + j > 0 && j0 + j < a.n) {
-                    const bool ao = (a.role_mask >> (j0 + j)) & 1u;
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-#pragma unroll
-                        for (int e = 0; e < EPV; ++e) acc[u].e[e] = pfold_step<F>(acc[u].e[e], x[j][u].e[e], ao);
-                }
-            }
+            load_chunk<NT, u32x4>(x, a.src, a.order, v0 * sizeof(T), j0, a.n, base, nt, nvec);
+            fold_chunk<F, false>(acc, x, j0, a.n, a.role_mask);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const size_t v = base + (size_t)u * nt;
             if (v < nvec) {
-                u32x4p raw;
+                u32x4 raw;
                 __builtin_memcpy(&raw, &acc[u], 16);
                 if (wt) __builtin_amdgcn_raw_buffer_store_b128(raw, rs, (unsigned)(v * 16), 0, kSysCoherent);
-                else pstore<NT>(dst + v0 + v * EPV, raw);
+                else vstore<NT>(dst + v0 + v * EPV, raw);
             }
         }
     }
@@ -139,51 +83,42 @@ template <class F, bool NT> __device__ void fold_range(const PipeArgs &a, size_t
     constexpr int EPV = 16 / sizeof(T);
     T *dst = reinterpret_cast<T *>(a.dst);
     const size_t t = threadIdx.x, nt = blockDim.x;
-    size_t head = hi - lo, nvec = 0;
-    if (a.co_fold) {
-        const uintptr_t mis = ((uintptr_t)(dst + lo)) & 15;
-        head = mis ? (16 - mis) / sizeof(T) : 0;
-        if (head > hi - lo) head = hi - lo;
-        nvec = (hi - lo - head) / EPV;
-    }
-    for (size_t i = lo + t; i < lo + head; i += nt) dst[i] = pfold_scalar<F>(a, i);
+    static_assert((sizeof(T) & (sizeof(T) - 1)) == 0 && sizeof(T) <= 16, "the mask below is 16 - sizeof(T)");
+    // (dst holds whole elements -- co_fold says so, coll_pipe_host.cpp; masking the element's low bits
+    // out of m lets the compiler see it, and split16's whole-element test costs no registers)
+    const Split16 sp = split16(hi - lo, sizeof(T), (uintptr_t)(dst + lo) & (16 - sizeof(T)), a.co_fold);
+    const size_t head = sp.head, nvec = sp.nvec;
+    for (size_t i = lo + t; i < lo + head; i += nt)
+        dst[i] = fold_scalar<F, false>(a.src, a.order, a.role_mask, a.n, i);
     const size_t v0 = lo + head;  // first element of the vector body
     if (a.n <= 4)
         fold_body<F, NT, 4, 4>(a, dst, v0, nvec, wt);
     else
         fold_body<F, NT, 2, kFoldChunk>(a, dst, v0, nvec, wt);
-    for (size_t i = v0 + nvec * EPV + t; i < hi; i += nt) dst[i] = pfold_scalar<F>(a, i);
+    for (size_t i = v0 + nvec * EPV + t; i < hi; i += nt)
+        dst[i] = fold_scalar<F, false>(a.src, a.order, a.role_mask, a.n, i);
 }
 
 // copy bytes [lo, hi) (absolute byte offsets) from src to dst
 template <bool NT> __device__ void copy_range(char *dst, const char *src, size_t lo, size_t hi, bool co, bool wt)
 {
     const size_t t = threadIdx.x, nt = blockDim.x;
-    size_t head = hi - lo, nvec = 0;
-    if (co) {
-        const uintptr_t mis = ((uintptr_t)(dst + lo)) & 15;
-        head = mis ? 16 - mis : 0;
-        if (head > hi - lo) head = hi - lo;
-        nvec = (hi - lo - head) / 16;
-    }
+    const Split16 sp = split16(hi - lo, 1, (uintptr_t)(dst + lo) & 15, co);
+    const size_t head = sp.head, nvec = sp.nvec;
     for (size_t i = lo + t; i < lo + head; i += nt) dst[i] = src[i];
     const size_t b0 = lo + head;
     constexpr int U = 8;
     const __amdgpu_buffer_rsrc_t rs = wt_rsrc(src + b0);
     for (size_t base = t; base < nvec; base += nt * U) {
-        u32x4p x[U];
+        u32x4 x[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const size_t v = base + (size_t)u * nt;
             if (v < nvec)
                 x[u] = wt ? __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)(v * 16), 0, kSysCoherent)
-                          : pload<NT>(src + b0 + v * 16);
+                          : vload<NT, u32x4>(src + b0 + v * 16);
         }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t v = base + (size_t)u * nt;
-            if (v < nvec) pstore<NT>(dst + b0 + v * 16, x[u]);
-        }
+        store_vecs<NT>(dst + b0, x, base, nt, nvec);
     }
     for (size_t i = b0 + nvec * 16 + t; i < hi; i += nt) dst[i] = src[i];
 }
@@ -276,7 +211,7 @@ template <class F, bool NT> __global__ __launch_bounds__(256) void k_pipe_allred
     }
 }
 
-static bool pipe_nt(size_t bytes) { return 2 * bytes > ((size_t)256 << 20); }
+static bool pipe_nt(size_t bytes) { return beyond_mall(2 * bytes); }
 
 template <class F> static int launch_pipe(const PipeArgs &a, unsigned grid, hipStream_t s)
 {

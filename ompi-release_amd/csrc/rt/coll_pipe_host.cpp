@@ -34,6 +34,7 @@
 #include "coll_internal.hpp"
 #include "coll_sched.hpp"
 #include "rt_internal.hpp"
+#include "stream_core.hpp"
 
 #include "comm_internal.hpp"
 
@@ -127,12 +128,14 @@ int pipe_allreduce(mi355x_comm *c, int op, int type, const Program &pr,
     a.role_mask = pr.role_mask;
     // vector paths: every fold operand shares the destination's misalignment (a whole element);
     // a pull needs only its source and destination to agree
-    const uintptr_t m = (uintptr_t)a.dst & 15;
     a.wt = coll_tune().pipe_wt;
-    a.co_fold = (m % esz) == 0;
-    for (int q = 0; q < c->size && a.co_fold; ++q) a.co_fold = (((uintptr_t)a.src[q]) & 15) == m;
-    for (int q = 0; q < c->size; ++q)
-        if ((((uintptr_t)a.peer_rbuf[q]) & 15) == m) a.co_pull |= 1ull << q;
+    const void *fold_ptrs[1 + kMaxRanks] = {a.dst};
+    for (int q = 0; q < c->size; ++q) fold_ptrs[1 + q] = a.src[q];
+    a.co_fold = co_aligned(esz, fold_ptrs, 1 + c->size);
+    for (int q = 0; q < c->size; ++q) {
+        const void *const pull_ptrs[] = {a.dst, a.peer_rbuf[q]};
+        if (co_aligned(1, pull_ptrs, 2)) a.co_pull |= 1ull << q;
+    }
     // persistent grid: pipe_wg_per_cu workgroups of 256 per CU, split among the ranks sharing
     // this GPU.  Ranks that share a GPU must all be resident at once (rank A's pull items spin
     // until rank B's fold items have run), so their grids together stay within what the CUs hold.

@@ -62,7 +62,7 @@ template <class F> __device__ __forceinline__ typename F::T svc_ring_fold(const 
 template <class F> static __device__ void svc_pull(const LLArgs &a, const SvcCall &sc, uint64_t stride)
 {
     using T = typename F::T;
-    using V = LLVec<T>;
+    using V = Vec16<T>;
     constexpr int EPV = 16 / sizeof(T);
     const uint64_t nvec = a.nbytes / 16;
     // kSvcPullU vectors per lane per pass, every source's loads of the pass issued before any
@@ -78,7 +78,7 @@ template <class F> static __device__ void svc_pull(const LLArgs &a, const SvcCal
             for (int u = 0; u < kSvcPullU; ++u) {
                 const uint64_t v = v0 + (uint64_t)u * step;
                 if (v >= nvec) continue;
-                const u32x4l raw = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)(v * 16), 0, kLLSysCoherent);
+                const u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)(v * 16), 0, kSysCoherent);
                 __builtin_memcpy(&xv[u][q], &raw, 16);
             }
         }
@@ -94,9 +94,9 @@ template <class F> static __device__ void svc_pull(const LLArgs &a, const SvcCal
                 for (int q = 0; q < kLLMaxRanks; ++q) X.set(q, xv[u][q].e[e]);
                 r.e[e] = svc_ring_fold<F>(a, v * EPV + e, X);
             }
-            u32x4l out;
+            u32x4 out;
             __builtin_memcpy(&out, &r, 16);
-            __builtin_amdgcn_raw_buffer_store_b128(out, ll_rsrc(a.dst), (unsigned)(v * 16), 0, kLLSysCoherent);
+            __builtin_amdgcn_raw_buffer_store_b128(out, ll_rsrc(a.dst), (unsigned)(v * 16), 0, kSysCoherent);
         }
     }
     const uint64_t i = nvec * EPV + threadIdx.x;  // the tail: fewer than EPV elements
@@ -130,29 +130,29 @@ static __device__ void svc_copy_seg(const char *src, char *dst, uint64_t len, ui
     if (((((uintptr_t)src) | ((uintptr_t)dst) | len) & 15) == 0) {
         const uint64_t nvec = len / 16;
         for (uint64_t v0 = first; v0 < nvec; v0 += step * kSvcPullU) {
-            u32x4l x[kSvcPullU];
+            u32x4 x[kSvcPullU];
 #pragma unroll
             for (int u = 0; u < kSvcPullU; ++u) {
                 const uint64_t v = v0 + (uint64_t)u * step;
-                if (v < nvec) x[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)(v * 16), 0, kLLSysCoherent);
+                if (v < nvec) x[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)(v * 16), 0, kSysCoherent);
             }
 #pragma unroll
             for (int u = 0; u < kSvcPullU; ++u) {
                 const uint64_t v = v0 + (uint64_t)u * step;
-                if (v < nvec) __builtin_amdgcn_raw_buffer_store_b128(x[u], rd, (unsigned)(v * 16), 0, kLLSysCoherent);
+                if (v < nvec) __builtin_amdgcn_raw_buffer_store_b128(x[u], rd, (unsigned)(v * 16), 0, kSysCoherent);
             }
         }
         return;
     }
     if (((((uintptr_t)src) | ((uintptr_t)dst) | len) & 3) == 0) {
         for (uint64_t w = first; w < len / 4; w += step)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(w * 4), 0, kLLSysCoherent),
-                                                  rd, (unsigned)(w * 4), 0, kLLSysCoherent);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(w * 4), 0, kSysCoherent),
+                                                  rd, (unsigned)(w * 4), 0, kSysCoherent);
         return;
     }
     for (uint64_t b = first; b < len; b += step)
-        __builtin_amdgcn_raw_buffer_store_b8(__builtin_amdgcn_raw_buffer_load_b8(rs, (unsigned)b, 0, kLLSysCoherent), rd,
-                                             (unsigned)b, 0, kLLSysCoherent);
+        __builtin_amdgcn_raw_buffer_store_b8(__builtin_amdgcn_raw_buffer_load_b8(rs, (unsigned)b, 0, kSysCoherent), rd,
+                                             (unsigned)b, 0, kSysCoherent);
 }
 
 // LL_PULL_AG / LL_PULL_BC: allgather (block q from rank q's input, own block skipped in place) and

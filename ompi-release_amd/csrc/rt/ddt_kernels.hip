@@ -18,13 +18,13 @@
 
 #include "ddt_internal.hpp"
 #include "rt_internal.hpp"
+#include "stream_core.hpp"
 
 #include <mutex>
 #include <vector>
 
 namespace mi355x {
 
-typedef unsigned int u32x4d __attribute__((ext_vector_type(4)));
 // the same 16 bytes at an address only 4-B aligned (the memory side of k_ddt_units_wide): the
 // type's alignment says so, so the compiler may not assume 16 (the dwordx4 access is legal on any
 // 4-B boundary)
@@ -88,13 +88,13 @@ __global__ __launch_bounds__(1024) void k_csum_finish(CsumSink k)
     // tens of thousands of partials through one workgroup: 16-B loads, 8 in flight per lane
     unsigned a = 0;
     const unsigned nv = k.nblocks / 4;
-    const u32x4d *pv = reinterpret_cast<const u32x4d *>(k.partial);
+    const u32x4 *pv = reinterpret_cast<const u32x4 *>(k.partial);
     for (unsigned base = threadIdx.x; base < nv; base += 8 * blockDim.x) {
-        u32x4d v[8];
+        u32x4 v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const unsigned i = base + u * blockDim.x;
-            v[u] = i < nv ? pv[i] : u32x4d{0, 0, 0, 0};
+            v[u] = i < nv ? pv[i] : u32x4{0, 0, 0, 0};
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) a += v[u].x + v[u].y + v[u].z + v[u].w;
@@ -118,13 +118,13 @@ __global__ __launch_bounds__(256) void k_ddt(DdtDev d, char *mem, char *packed, 
         Where w = locate(d, p0);
         if (p0 >= pos && p0 + 16 <= pos + bytes && w.left >= 16 && ((w.mem + (int64_t)(uintptr_t)mem) & 15) == 0 &&
             (((uintptr_t)pk) & 15) == 0) {
-            u32x4d v;
+            u32x4 v;
             if constexpr (PACK) {
-                v = *reinterpret_cast<const u32x4d *>(mem + w.mem);
-                *reinterpret_cast<u32x4d *>(pk) = v;
+                v = *reinterpret_cast<const u32x4 *>(mem + w.mem);
+                *reinterpret_cast<u32x4 *>(pk) = v;
             } else {
-                v = *reinterpret_cast<const u32x4d *>(pk);
-                *reinterpret_cast<u32x4d *>(mem + w.mem) = v;
+                v = *reinterpret_cast<const u32x4 *>(pk);
+                *reinterpret_cast<u32x4 *>(mem + w.mem) = v;
             }
             if constexpr (CSUM) acc += v.x + v.y + v.z + v.w;
         } else {
@@ -192,7 +192,7 @@ struct RowArgs {
 };
 
 template <int W> struct SlotT;
-template <> struct SlotT<16> { typedef u32x4d type; };
+template <> struct SlotT<16> { typedef u32x4 type; };
 template <> struct SlotT<8> { typedef unsigned long long type; };
 template <> struct SlotT<4> { typedef unsigned type; };
 template <> struct SlotT<2> { typedef unsigned short type; };
@@ -557,7 +557,7 @@ __global__ __launch_bounds__(256) void k_ddt_units_wide(UnitArgs a, CsumSink csu
     const uint32_t tpb = blockDim.x, stride = gridDim.x * tpb * kUnitU;
     unsigned acc = 0;
     for (uint32_t base = blockIdx.x * tpb * kUnitU + threadIdx.x; base < nslots; base += stride) {
-        u32x4d v[kUnitU];
+        u32x4 v[kUnitU];
         char *mp[kUnitU];   // the slot's memory address when it lies inside one run, else NULL
         bool live[kUnitU];
 #pragma unroll
@@ -578,7 +578,7 @@ __global__ __launch_bounds__(256) void k_ddt_units_wide(UnitArgs a, CsumSink csu
             if (o + UPS <= rl) {
                 mp[u] = m0;
                 v[u] = PACK ? *reinterpret_cast<const u32x4a4 *>(m0)
-                            : *reinterpret_cast<const u32x4d *>(a.packed + (size_t)i * 16);
+                            : *reinterpret_cast<const u32x4 *>(a.packed + (size_t)i * 16);
                 continue;
             }
             // the slot crosses a run boundary: unit by unit
@@ -601,13 +601,13 @@ __global__ __launch_bounds__(256) void k_ddt_units_wide(UnitArgs a, CsumSink csu
                 }
             }
             if (PACK) __builtin_memcpy(&v[u], part, 16);
-            else v[u] = *reinterpret_cast<const u32x4d *>(a.packed + (size_t)i * 16);
+            else v[u] = *reinterpret_cast<const u32x4 *>(a.packed + (size_t)i * 16);
         }
 #pragma unroll
         for (int u = 0; u < kUnitU; ++u) {
             if (!live[u]) continue;
             const uint32_t i = base + (uint32_t)u * tpb;
-            if (PACK) *reinterpret_cast<u32x4d *>(a.packed + (size_t)i * 16) = v[u];
+            if (PACK) *reinterpret_cast<u32x4 *>(a.packed + (size_t)i * 16) = v[u];
             else if (mp[u]) *reinterpret_cast<u32x4a4 *>(mp[u]) = v[u];
             if constexpr (CSUM) acc += slot_csum<16>(v[u], 0);
         }
@@ -684,7 +684,7 @@ __global__ __launch_bounds__(256) void k_ddt_runs_unpack(RunsArgs a)
     const int64_t end = h + ((len - h) & ~(int64_t)15);
     if (lane < h / W) *reinterpret_cast<S *>(m + lane * W) = *reinterpret_cast<const S *>(pk + lane * W);
     for (int64_t o = h + (int64_t)lane * 16; o < end; o += 64 * 16)
-        *reinterpret_cast<u32x4d *>(m + o) = *reinterpret_cast<const u32x4a4 *>(pk + o);
+        *reinterpret_cast<u32x4 *>(m + o) = *reinterpret_cast<const u32x4a4 *>(pk + o);
     if (lane < (len - end) / W)
         *reinterpret_cast<S *>(m + end + lane * W) = *reinterpret_cast<const S *>(pk + end + lane * W);
 }

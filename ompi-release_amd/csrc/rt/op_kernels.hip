@@ -11,22 +11,19 @@
 //     per lane, blocks_per_cu x CUs) serves misaligned operands and tuning.
 //   * scalar head/tail so any alignment works: when all three operands share the same
 //     misalignment mod 16 the head peels to a 16-B boundary; otherwise the whole range takes
-//     the element-wise path (still coalesced, one element per lane).
+//     the element-wise path (still coalesced, one element per lane).  The split, the vector
+//     access and the grid arithmetic are stream_core.hpp's, shared with the engine's kernels.
 //   * no MFMA, no LDS: the work is 2 reads + 1 write per element -> HBM bound.
 // Algorithmic bytes per call = 3 x count x sizeof(T) (2-buff: read in, read+write inout;
 // 3-buff: read in1, in2, write out).
 #include "op_functors.hpp"
 #include "rt_internal.hpp"
+#include "slot_list.hpp"
+#include "stream_core.hpp"
 
 #include <type_traits>
 
 namespace mi355x {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct alignas(16) Vec16 {
-    T e[16 / sizeof(T)];
-};
 
 struct StreamArgs {
     const void *a;    // 2-buff: in (source)          3-buff: in1
@@ -71,30 +68,7 @@ __device__ __forceinline__ u32x4 apply_vec(const u32x4 &ra, const u32x4 &rb)
     return out;
 }
 
-template <bool NT, typename V> __device__ __forceinline__ V vload(const V *p)
-{
-    u32x4 raw;
-    if constexpr (NT)
-        raw = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
-    else
-        raw = *reinterpret_cast<const u32x4 *>(p);
-    V v;
-    __builtin_memcpy(&v, &raw, 16);
-    return v;
-}
-
-template <bool NT, typename V> __device__ __forceinline__ void vstore(V *p, const V &v)
-{
-    u32x4 raw;
-    __builtin_memcpy(&raw, &v, 16);
-    if constexpr (NT)
-        __builtin_nontemporal_store(raw, reinterpret_cast<u32x4 *>(p));
-    else
-        *reinterpret_cast<u32x4 *>(p) = raw;
-}
-
-// NTM bit 0: non-temporal loads, bit 1: non-temporal stores (streams larger than the 256 MiB
-// Infinity Cache gain ~9 % from not allocating in L2/MALL; small, re-read operands lose)
+// NTM bit 0: non-temporal loads, bit 1: non-temporal stores (beyond_mall, stream_core.hpp)
 template <class F, bool THREE, int U, int NTM>
 __global__ __launch_bounds__(256) void k_stream(StreamArgs args)
 {
@@ -119,8 +93,8 @@ __global__ __launch_bounds__(256) void k_stream(StreamArgs args)
         for (int u = 0; u < U; ++u) {
             const size_t i = base + (size_t)u * nthr;
             if (i < nvec) {
-                xa[u] = vload<(NTM & 1) != 0>(av + i);
-                xb[u] = vload<(NTM & 1) != 0>(bv + i);
+                xa[u] = vload<(NTM & 1) != 0, V>(av + i);
+                xb[u] = vload<(NTM & 1) != 0, V>(bv + i);
             }
         }
 #pragma unroll
@@ -130,11 +104,7 @@ __global__ __launch_bounds__(256) void k_stream(StreamArgs args)
                 u32x4 ra, rb;
                 __builtin_memcpy(&ra, &xa[u], 16);
                 __builtin_memcpy(&rb, &xb[u], 16);
-                const u32x4 r = apply_vec<F, THREE>(ra, rb);
-                if constexpr ((NTM & 2) != 0)
-                    __builtin_nontemporal_store(r, reinterpret_cast<u32x4 *>(ov + i));
-                else
-                    *reinterpret_cast<u32x4 *>(ov + i) = r;
+                vstore<(NTM & 2) != 0>(ov + i, apply_vec<F, THREE>(ra, rb));
             }
         }
     }
@@ -214,8 +184,7 @@ static int launch_shape(const StreamArgs &args, hipStream_t s)
     using T = typename F::T;
     constexpr int EPV = 16 / sizeof(T);
     const StreamTune &t = stream_tune();
-    const size_t threads = 256;
-    const size_t scalar = args.head + (args.n - args.head - args.nvec * EPV);
+    const size_t scalar = args.n - args.nvec * EPV;  // head + tail
     if (t.mode == 1 && args.nvec > 0 && scalar <= 64) {
         // one-shot chunked grid (head/tail < 16 elements are handled by the edge blocks)
         const size_t tpb = (size_t)t.threads;
@@ -225,14 +194,8 @@ static int launch_shape(const StreamArgs &args, hipStream_t s)
         MI_HIP(hipGetLastError());
         return MI355X_SUCCESS;
     }
-    size_t work = args.nvec ? (args.nvec + (size_t)U - 1) / U : 0;
-    if (scalar > work) work = scalar;
-    size_t blocks = (work + threads - 1) / threads;
-    const size_t cap = (size_t)t.blocks_per_cu * (size_t)device_cu_count();
-    if (blocks > cap) blocks = cap;
-    if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL((k_stream<F, THREE, U, NTM>), dim3((unsigned)blocks), dim3(threads), 0, s,
-                       args);
+    const size_t blocks = grid_for_split(Split16{args.head, args.nvec}, args.n, EPV, U, t.blocks_per_cu);
+    hipLaunchKernelGGL((k_stream<F, THREE, U, NTM>), dim3((unsigned)blocks), dim3(256), 0, s, args);
     MI_HIP(hipGetLastError());
     return MI355X_SUCCESS;
 }
@@ -368,7 +331,7 @@ static int launch(const void *a, const void *b, void *out, size_t n, hipStream_t
         if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0 && n < ((size_t)1 << 40)) {
             const size_t nhalf = 2 * n;
             const size_t blocks = (nhalf + 1023) / 1024;
-            const bool nt = 3 * n * sizeof(T) > ((size_t)256 << 20);
+            const bool nt = beyond_mall(3 * n * sizeof(T));
             const u32x4 *ha = static_cast<const u32x4 *>(a), *hb = static_cast<const u32x4 *>(b);
             u32x4 *ho = static_cast<u32x4 *>(out);
             if (nt)
@@ -378,34 +341,25 @@ static int launch(const void *a, const void *b, void *out, size_t n, hipStream_t
             MI_HIP(hipGetLastError());
             return MI355X_SUCCESS;
         }
-        size_t blocks = (n + 255) / 256;
-        const size_t cap = (size_t)stream_tune().blocks_per_cu * (size_t)device_cu_count();
-        if (blocks > cap) blocks = cap;
+        const size_t blocks = grid_for(n, stream_tune().blocks_per_cu);
         hipLaunchKernelGGL((k_wide<F, THREE>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const T *>(a),
                            static_cast<const T *>(b), static_cast<T *>(out), n);
         MI_HIP(hipGetLastError());
         return MI355X_SUCCESS;
     } else {
-    constexpr size_t EPV = 16 / sizeof(T);
     StreamArgs args;
     args.a = a;
     args.b = b;
     args.out = out;
     args.n = n;
-    const uintptr_t ma = (uintptr_t)a & 15, mb = (uintptr_t)b & 15, mo = (uintptr_t)out & 15;
-    if (ma == mb && mb == mo && (ma % sizeof(T)) == 0) {
-        size_t head = ma ? (16 - ma) / sizeof(T) : 0;
-        if (head > n) head = n;
-        args.head = head;
-        args.nvec = (n - head) / EPV;
-    } else {
-        args.head = n; // element-wise path
-        args.nvec = 0;
-    }
+    const void *const ptrs[] = {a, b, out};
+    const Split16 sp = split16(n, sizeof(T), (uintptr_t)a & 15, co_aligned(sizeof(T), ptrs, 3));
+    args.head = sp.head;  // == n: element-wise path
+    args.nvec = sp.nvec;
     const StreamTune &t = stream_tune();
     // non-temporal policy: explicit 0..3, or auto (-1): streams beyond the Infinity Cache
     int ntm = t.nontemporal;
-    if (ntm < 0) ntm = (3 * n * sizeof(T) > ((size_t)256 << 20)) ? 3 : 0;
+    if (ntm < 0) ntm = beyond_mall(3 * n * sizeof(T)) ? 3 : 0;
     if constexpr (Tunable<F>::value) {
 #define MI_NT(U_)                                                              \
     switch (ntm) {                                                             \
@@ -436,78 +390,18 @@ struct Slot {
     launch_fn three = nullptr;
 };
 
-template <class F> static void put(Slot (&tab)[MI355X_OP_MAX_][MI355X_T_MAX], int op, int ty)
-{
-    tab[op][ty].two = &launch<F, false>;
-    tab[op][ty].three = &launch<F, true>;
-}
-
-template <template <typename> class OP>
-static void put_ints(Slot (&tab)[MI355X_OP_MAX_][MI355X_T_MAX], int op)
-{
-    put<OP<int8_t>>(tab, op, MI355X_T_INT8);
-    put<OP<uint8_t>>(tab, op, MI355X_T_UINT8);
-    put<OP<int16_t>>(tab, op, MI355X_T_INT16);
-    put<OP<uint16_t>>(tab, op, MI355X_T_UINT16);
-    put<OP<int32_t>>(tab, op, MI355X_T_INT32);
-    put<OP<uint32_t>>(tab, op, MI355X_T_UINT32);
-    put<OP<int64_t>>(tab, op, MI355X_T_INT64);
-    put<OP<uint64_t>>(tab, op, MI355X_T_UINT64);
-}
-
 struct Table {
     Slot s[MI355X_OP_MAX_][MI355X_T_MAX];
     Table()
     {
-        // groups as in op_base_functions.c:1373-1457 (Fortran types disabled)
-        put_ints<OpMax>(s, MI355X_OP_MAX);
-        put<OpMax<float>>(s, MI355X_OP_MAX, MI355X_T_FLOAT);
-        put<OpMax<double>>(s, MI355X_OP_MAX, MI355X_T_DOUBLE);
-        put_ints<OpMin>(s, MI355X_OP_MIN);
-        put<OpMin<float>>(s, MI355X_OP_MIN, MI355X_T_FLOAT);
-        put<OpMin<double>>(s, MI355X_OP_MIN, MI355X_T_DOUBLE);
-        put_ints<OpSum>(s, MI355X_OP_SUM);
-        put<OpSum<float>>(s, MI355X_OP_SUM, MI355X_T_FLOAT);
-        put<OpSum<double>>(s, MI355X_OP_SUM, MI355X_T_DOUBLE);
-        put<OpCsum<cf32>>(s, MI355X_OP_SUM, MI355X_T_C_FLOAT_COMPLEX);
-        put<OpCsum<cf64>>(s, MI355X_OP_SUM, MI355X_T_C_DOUBLE_COMPLEX);
-        put_ints<OpProd>(s, MI355X_OP_PROD);
-        put<OpProd<float>>(s, MI355X_OP_PROD, MI355X_T_FLOAT);
-        put<OpProd<double>>(s, MI355X_OP_PROD, MI355X_T_DOUBLE);
-        put<OpCprod<cf32>>(s, MI355X_OP_PROD, MI355X_T_C_FLOAT_COMPLEX);
-        put<OpCprod<cf64>>(s, MI355X_OP_PROD, MI355X_T_C_DOUBLE_COMPLEX);
-        put_ints<OpLand>(s, MI355X_OP_LAND);
-        put<OpLand<uint8_t>>(s, MI355X_OP_LAND, MI355X_T_BOOL);
-        put_ints<OpLor>(s, MI355X_OP_LOR);
-        put<OpLor<uint8_t>>(s, MI355X_OP_LOR, MI355X_T_BOOL);
-        put_ints<OpLxor>(s, MI355X_OP_LXOR);
-        put<OpLxor<uint8_t>>(s, MI355X_OP_LXOR, MI355X_T_BOOL);
-        put_ints<OpBand>(s, MI355X_OP_BAND);
-        put<OpBand<int8_t>>(s, MI355X_OP_BAND, MI355X_T_BYTE);
-        put_ints<OpBor>(s, MI355X_OP_BOR);
-        put<OpBor<int8_t>>(s, MI355X_OP_BOR, MI355X_T_BYTE);
-        put_ints<OpBxor>(s, MI355X_OP_BXOR);
-        put<OpBxor<int8_t>>(s, MI355X_OP_BXOR, MI355X_T_BYTE);
-        put<OpLoc<p_float_int, true>>(s, MI355X_OP_MAXLOC, MI355X_T_FLOAT_INT);
-        put<OpLoc<p_double_int, true>>(s, MI355X_OP_MAXLOC, MI355X_T_DOUBLE_INT);
-        put<OpLoc<p_long_int, true>>(s, MI355X_OP_MAXLOC, MI355X_T_LONG_INT);
-        put<OpLoc<p_2int, true>>(s, MI355X_OP_MAXLOC, MI355X_T_2INT);
-        put<OpLoc<p_short_int, true>>(s, MI355X_OP_MAXLOC, MI355X_T_SHORT_INT);
-        put<OpLoc<p_float_int, false>>(s, MI355X_OP_MINLOC, MI355X_T_FLOAT_INT);
-        put<OpLoc<p_double_int, false>>(s, MI355X_OP_MINLOC, MI355X_T_DOUBLE_INT);
-        put<OpLoc<p_long_int, false>>(s, MI355X_OP_MINLOC, MI355X_T_LONG_INT);
-        put<OpLoc<p_2int, false>>(s, MI355X_OP_MINLOC, MI355X_T_2INT);
-        put<OpLoc<p_short_int, false>>(s, MI355X_OP_MINLOC, MI355X_T_SHORT_INT);
-        // x87 long double: compare-and-select (MAX/MIN) and the x87 add / multiply restated in
-        // integer arithmetic (SUM/PROD, f80_arith.hpp), real and complex
-        put<OpMax<f80>>(s, MI355X_OP_MAX, MI355X_T_LONG_DOUBLE);
-        put<OpMin<f80>>(s, MI355X_OP_MIN, MI355X_T_LONG_DOUBLE);
-        put<OpSum<f80>>(s, MI355X_OP_SUM, MI355X_T_LONG_DOUBLE);
-        put<OpProd<f80>>(s, MI355X_OP_PROD, MI355X_T_LONG_DOUBLE);
-        put<OpCsum<cf80>>(s, MI355X_OP_SUM, MI355X_T_C_LONG_DOUBLE_COMPLEX);
-        put<OpCprod<cf80>>(s, MI355X_OP_PROD, MI355X_T_C_LONG_DOUBLE_COMPLEX);
-        put<OpLoc<p_ldouble_int, true>>(s, MI355X_OP_MAXLOC, MI355X_T_LONG_DOUBLE_INT);
-        put<OpLoc<p_ldouble_int, false>>(s, MI355X_OP_MINLOC, MI355X_T_LONG_DOUBLE_INT);
+        // the engine's slots and the four 32-byte ones only op/hip's kernels reduce (slot_list.hpp)
+        auto put = [&](auto tag, int op, int ty) {
+            using F = typename decltype(tag)::type;
+            s[op][ty].two = &launch<F, false>;
+            s[op][ty].three = &launch<F, true>;
+        };
+        for_each_slot(put);
+        for_each_wide_slot(put);
     }
 };
 

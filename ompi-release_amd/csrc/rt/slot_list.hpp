@@ -1,7 +1,8 @@
 // slot_list.hpp -- the (MPI_Op, element type) slots that have a GPU kernel, as one list shared by
-// the kernel families (the 3-buff table of op_base_functions.c:1460-1543 minus the two 32-byte
-// types -- MPI_LONG_DOUBLE_INT and C_LONG_DOUBLE_COMPLEX -- which op/hip's kernels reduce but the
-// engine's 16-byte-vector families do not carry: the engine serves those by gather-then-fold).
+// the kernel families: the 3-buff table of op_base_functions.c:1460-1543 (groups as in :1373-1457,
+// Fortran types disabled).  for_each_slot leaves out the two 32-byte types -- MPI_LONG_DOUBLE_INT
+// and C_LONG_DOUBLE_COMPLEX -- which op/hip's kernels reduce but the engine's 16-byte-vector
+// families do not carry (the engine serves those by gather-then-fold); for_each_wide_slot lists them.
 //
 //   for_each_slot([&](auto tag, int op, int type) { using F = typename decltype(tag)::type; ... });
 #pragma once
@@ -72,6 +73,15 @@ template <class Put> __host__ __device__ inline void for_each_slot(Put &&put)
     put(SlotTag<OpMin<f80>>{}, MI355X_OP_MIN, MI355X_T_LONG_DOUBLE);
     put(SlotTag<OpSum<f80>>{}, MI355X_OP_SUM, MI355X_T_LONG_DOUBLE);
     put(SlotTag<OpProd<f80>>{}, MI355X_OP_PROD, MI355X_T_LONG_DOUBLE);
+}
+
+// the 32-byte element types: x87 complex SUM / PROD and the long double value-index pairs
+template <class Put> __host__ __device__ inline void for_each_wide_slot(Put &&put)
+{
+    put(SlotTag<OpCsum<cf80>>{}, MI355X_OP_SUM, MI355X_T_C_LONG_DOUBLE_COMPLEX);
+    put(SlotTag<OpCprod<cf80>>{}, MI355X_OP_PROD, MI355X_T_C_LONG_DOUBLE_COMPLEX);
+    put(SlotTag<OpLoc<p_ldouble_int, true>>{}, MI355X_OP_MAXLOC, MI355X_T_LONG_DOUBLE_INT);
+    put(SlotTag<OpLoc<p_ldouble_int, false>>{}, MI355X_OP_MINLOC, MI355X_T_LONG_DOUBLE_INT);
 }
 
 } // namespace mi355x
