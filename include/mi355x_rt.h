@@ -264,13 +264,16 @@ enum mi355x_knob {
                                            own selection, every step the 3-buff rule with the rank's own data
                                            as in1); with 1 mi355x_iscan / _iexscan also run libnbc's form of
                                            the rank chain.  Set only while no nonblocking call is pending. */
-    MI355X_KNOB_SCAN_PART_MIN_BYTES = 45 /* (per communicator, same value on every rank; env
+    MI355X_KNOB_SCAN_PART_MIN_BYTES = 45,/* (per communicator, same value on every rank; env
                                            MI355X_SCAN_PART_MIN_BYTES at creation; default 0: in the one-GPU
                                            rehearsal the chain is ahead below 64 MiB per rank) scan /
                                            exscan calls of at least this many bytes per rank, blocking or
                                            nonblocking, take the partitioned flow (see mi355x_scan); 0 = never.
                                            The results do not depend on it.  Set only while no nonblocking call
                                            is pending. */
+    MI355X_KNOB_MOVE_FUSED = 46          /* (read-only) movement calls of this communicator whose pull went
+                                           through a receive layout (the _ddt forms below): this rank unpacked
+                                           its peers' bytes straight from their memory */
 };
 /* cross-device flows (MI355X_KNOB_FLOWS) */
 enum mi355x_flow {
@@ -359,6 +362,30 @@ int mi355x_allgatherv(mi355x_comm_t *comm, const void *sbuf, size_t sbytes, void
 int mi355x_alltoall(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes, void *stream);
 int mi355x_alltoallv(mi355x_comm_t *comm, const void *sbuf, const size_t *scounts, const size_t *sdispls,
                      void *rbuf, const size_t *rcounts, const size_t *rdispls, void *stream);
+typedef struct mi355x_ddt mi355x_ddt_t;  /* a datatype layout of the GPU convertor (mi355x_ddt_create..., below) */
+/* The same four calls pulling straight into a derived receive datatype: what this rank receives goes
+ * from the owners' memory into `rddt` laid at rbuf in one pass -- no dense receive buffer, no unpack
+ * afterwards.  rcounts (scatterv: rcount) are INSTANCES of rddt; piece q starts at rbuf + rdispls[q]
+ * BYTES and takes the first bytes of its packed stream that the sender sends: at most
+ * rcounts[q] * mi355x_ddt_size(rddt) (more fails with MI355X_ERR_TRUNCATE); fewer end inside an
+ * instance or inside a run and leave the rest of the piece untouched.  The send side is as in the
+ * plain forms (bytes), and every step before the pull is theirs, so in one collective some ranks
+ * may call a _ddt form and the others the plain one.  A layout of one run per block (vector,
+ * subarray rows, a resized column) takes one launch for all peers; a layout with several runs per
+ * block one per peer.  rddt NULL (counts are then bytes) or a layout without gaps is the plain
+ * call.  MPI_IN_PLACE with a layout that has gaps (sbuf NULL in allgatherv / alltoallv, or at the
+ * root of gatherv) returns MI355X_ERR_UNSUPPORTED before the rank meets its peers.  Calls that
+ * pull this way are counted by MI355X_KNOB_MOVE_FUSED.  rddt is not read on a rank that receives
+ * nothing (gatherv off the root). */
+int mi355x_gatherv_ddt(mi355x_comm_t *comm, const void *sbuf, size_t sbytes, void *rbuf, const mi355x_ddt_t *rddt,
+                       const size_t *rcounts, const size_t *rdispls, int root, void *stream);
+int mi355x_scatterv_ddt(mi355x_comm_t *comm, const void *sbuf, const size_t *scounts, const size_t *sdispls,
+                        void *rbuf, const mi355x_ddt_t *rddt, size_t rcount, int root, void *stream);
+int mi355x_allgatherv_ddt(mi355x_comm_t *comm, const void *sbuf, size_t sbytes, void *rbuf, const mi355x_ddt_t *rddt,
+                          const size_t *rcounts, const size_t *rdispls, void *stream);
+int mi355x_alltoallv_ddt(mi355x_comm_t *comm, const void *sbuf, const size_t *scounts, const size_t *sdispls,
+                         void *rbuf, const mi355x_ddt_t *rddt, const size_t *rcounts, const size_t *rdispls,
+                         void *stream);
 int mi355x_scan(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t count, int type, int op, void *stream);
 int mi355x_exscan(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t count, int type, int op, void *stream);
 /* The partitioned scan flow's layout (host only, no GPU needed): owner q's block of a count-element

@@ -175,6 +175,10 @@ def _declare(lib: ctypes.CDLL) -> None:
         "mi355x_allgatherv": (i, [vp, vp, sz, vp, c.POINTER(sz), c.POINTER(sz), vp]),
         "mi355x_alltoall": (i, [vp, vp, vp, sz, vp]),
         "mi355x_alltoallv": (i, [vp, vp, c.POINTER(sz), c.POINTER(sz), vp, c.POINTER(sz), c.POINTER(sz), vp]),
+        "mi355x_gatherv_ddt": (i, [vp, vp, sz, vp, vp, c.POINTER(sz), c.POINTER(sz), i, vp]),
+        "mi355x_scatterv_ddt": (i, [vp, vp, c.POINTER(sz), c.POINTER(sz), vp, vp, sz, i, vp]),
+        "mi355x_allgatherv_ddt": (i, [vp, vp, sz, vp, vp, c.POINTER(sz), c.POINTER(sz), vp]),
+        "mi355x_alltoallv_ddt": (i, [vp, vp, c.POINTER(sz), c.POINTER(sz), vp, vp, c.POINTER(sz), c.POINTER(sz), vp]),
         "mi355x_scan": (i, [vp, vp, vp, sz, i, i, vp]),
         "mi355x_exscan": (i, [vp, vp, vp, sz, i, i, vp]),
         "mi355x_iscan": (i, [vp, vp, vp, sz, i, i, vp, c.POINTER(vp)]),
@@ -283,7 +287,7 @@ KNOB = {"ALLREDUCE_ALG": 1, "REDUCE_ALG": 2, "REDUCE_SCATTER_ALG": 3, "BLOCKS_PE
         "SVC_OWNER": 33, "SVC_CLAIMS": 34, "SVC_IDLE_US": 35,
         "SVC_SHRINK_US": 36, "SVC_REGROWS": 37, "DEV_SETUP": 38, "SETUP_US": 39, "SELFTEST": 40,
         "PIPE_CALLS": 41, "EXPORT_MISMATCHES": 42, "SELFTEST_REUSED": 43, "NB_ORDER": 44,
-        "SCAN_PART_MIN_BYTES": 45}
+        "SCAN_PART_MIN_BYTES": 45, "MOVE_FUSED": 46}
 # coll/libnbc's algorithms (mi355x_comm_last_algorithm under NB_ORDER = 1, mi355x_nbc_decision)
 NBC_ALG = {"BINOMIAL": 101, "RING": 102, "CHAIN": 103}
 FLOW = {"SVC_LL": 1, "SVC_PULL": 2, "SVC_COPY": 4, "SVC_RS": 8, "PIPE": 16}
@@ -435,6 +439,25 @@ class Comm:
     def alltoallv(self, sbuf, scounts, sdispls, rbuf, rcounts, rdispls, stream=None) -> None:
         check(rt().mi355x_alltoallv(self.h, sbuf, self._sizes(scounts), self._sizes(sdispls), rbuf,
                                     self._sizes(rcounts), self._sizes(rdispls), stream), "mi355x_alltoallv")
+
+    # ---- the same pulling straight into a receive layout: rcounts in instances of rddt (a Ddt, or
+    #      None: bytes, the plain call), rdispls in bytes
+    def gatherv_ddt(self, sbuf, sbytes, rbuf, rddt, rcounts, rdispls, root, stream=None) -> None:
+        check(rt().mi355x_gatherv_ddt(self.h, sbuf, sbytes, rbuf, rddt.h if rddt else None, self._sizes(rcounts),
+                                      self._sizes(rdispls), root, stream), "mi355x_gatherv_ddt")
+
+    def scatterv_ddt(self, sbuf, scounts, sdispls, rbuf, rddt, rcount, root, stream=None) -> None:
+        check(rt().mi355x_scatterv_ddt(self.h, sbuf, self._sizes(scounts), self._sizes(sdispls), rbuf,
+                                       rddt.h if rddt else None, rcount, root, stream), "mi355x_scatterv_ddt")
+
+    def allgatherv_ddt(self, sbuf, sbytes, rbuf, rddt, rcounts, rdispls, stream=None) -> None:
+        check(rt().mi355x_allgatherv_ddt(self.h, sbuf, sbytes, rbuf, rddt.h if rddt else None, self._sizes(rcounts),
+                                         self._sizes(rdispls), stream), "mi355x_allgatherv_ddt")
+
+    def alltoallv_ddt(self, sbuf, scounts, sdispls, rbuf, rddt, rcounts, rdispls, stream=None) -> None:
+        check(rt().mi355x_alltoallv_ddt(self.h, sbuf, self._sizes(scounts), self._sizes(sdispls), rbuf,
+                                        rddt.h if rddt else None, self._sizes(rcounts), self._sizes(rdispls), stream),
+              "mi355x_alltoallv_ddt")
 
     def scan(self, sbuf, rbuf, count, ty, op, stream=None) -> None:
         check(rt().mi355x_scan(self.h, sbuf, rbuf, count, ty, op, stream), "mi355x_scan")

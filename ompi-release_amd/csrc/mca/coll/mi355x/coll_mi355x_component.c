@@ -539,6 +539,7 @@ typedef struct {
     mi355x_ddt_t *d;          /* NULL: dense, view == base */
     int host;                 /* host memory (a rank joining a call whose peers hold device buffers):
                                  the view is a device staging copy, moved by xstage */
+    int direct;               /* a derived device receive side the engine unpacks into itself: no view */
     const struct ompi_datatype_t *dt;
     char *view;
     size_t bytes[SIDE_MAX], off[SIDE_MAX], cnt[SIDE_MAX];
@@ -546,9 +547,10 @@ typedef struct {
 } side_t;
 
 /* counts/displacements in instances (NULL disps: consecutive pieces of `counts`; NULL counts:
- * every piece `count1` instances).  Returns OMPI_SUCCESS or an error. */
+ * every piece `count1` instances).  direct: a derived device layout takes no scratch -- the engine
+ * pulls straight into it (sides_engine); the side then has no view.  Returns OMPI_SUCCESS or an error. */
 static int side_init(mca_coll_mi355x_module_t *m, side_t *s, int slot, void *buf, const struct ompi_datatype_t *dt,
-                     int n, const int *counts, int count1, const int *disps)
+                     int n, const int *counts, int count1, const int *disps, int direct)
 {
     if (n > SIDE_MAX) return OMPI_ERR_NOT_SUPPORTED;
     memset(s, 0, sizeof(*s));
@@ -578,6 +580,11 @@ static int side_init(mca_coll_mi355x_module_t *m, side_t *s, int slot, void *buf
     if (!s->d && !dense(dt)) {
         fprintf(stderr, "[coll/mi355x] the GPU convertor cannot describe datatype %s\n", dt->name);
         return OMPI_ERR_NOT_SUPPORTED;
+    }
+    if (direct && s->d && !s->host) {
+        s->direct = 1;
+        for (int q = 0; q < n; ++q) s->direct = s->direct && s->udisp[q] >= 0;  /* (the engine's are unsigned) */
+        if (s->direct) return OMPI_SUCCESS;
     }
     size_t total = 0;
     for (int q = 0; q < n; ++q) {
@@ -1067,15 +1074,21 @@ static int movement_staged(mca_coll_mi355x_module_t *m, const movement_t *d, str
 
 /* The engine step of every call but allgather and bcast: the significant sides set up (scratch slot 0:
  * send, 1: receive), what this rank sends packed -- its send side whole; in place the receive side's piece
- * `me` (gather(v), allgatherv) or every piece (alltoall(v)) -- the engine's call, the receive side unpacked. */
+ * `me` (gather(v), allgatherv) or every piece (alltoall(v)) -- the engine's call, the receive side unpacked.
+ * A derived receive side in device memory, not in place, has no scratch and no unpack of its own: the
+ * engine's _ddt form pulls the peers' bytes straight into the layout (the fixed-count kinds through the
+ * v-forms, with the per-piece arrays of side_init).  Every rank still makes the same engine collective --
+ * the _ddt and the plain forms meet -- so the path depends on no rank-local layout; only the kernel of
+ * this rank's own pull does. */
 static int sides_engine(mca_coll_mi355x_module_t *m, const movement_t *d, struct ompi_communicator_t *comm)
 {
     const int me = mi355x_comm_rank_of(comm), root = d->root, ssig = d->s.sig, rsig = d->r.sig;
     const int every = d->kind == MOVE_ALLTOALL || d->kind == MOVE_ALLTOALLV;
     side_t snd, rcv;
     int rc = OMPI_SUCCESS;
-    if (ssig && (rc = side_init(m, &snd, 0, d->s.buf, d->s.dt, d->s.n, d->s.counts, d->s.count, d->s.disps))) return rc;
-    if (rsig && (rc = side_init(m, &rcv, 1, d->r.buf, d->r.dt, d->r.n, d->r.counts, d->r.count, d->r.disps))) return rc;
+    if (ssig && (rc = side_init(m, &snd, 0, d->s.buf, d->s.dt, d->s.n, d->s.counts, d->s.count, d->s.disps, 0))) return rc;
+    if (rsig && (rc = side_init(m, &rcv, 1, d->r.buf, d->r.dt, d->r.n, d->r.counts, d->r.count, d->r.disps, !d->inplace)))
+        return rc;
     if (d->kind == MOVE_ALLTOALL && ssig && snd.bytes[0] != rcv.bytes[0]) return OMPI_ERR_BAD_PARAM;
     int erc = ssig ? side_move(m, &snd, -1, 1) : d->inplace ? side_move(m, &rcv, every ? -1 : me, 1) : MI355X_SUCCESS;
     if (erc != MI355X_SUCCESS) return map_rc(erc);
@@ -1084,6 +1097,18 @@ static int sides_engine(mca_coll_mi355x_module_t *m, const movement_t *d, struct
     void *rv = rsig ? rcv.view : NULL;
     const size_t *sbytes = ssig ? snd.bytes : NULL, *soff = ssig ? snd.off : NULL;
     const size_t *rbytes = rsig ? rcv.bytes : NULL, *roff = rsig ? rcv.off : NULL;
+    if (rsig && rcv.direct) {
+        const size_t *rdis = (const size_t *)rcv.udisp;  /* (not negative: side_init) */
+        const size_t sb0 = ssig ? sbytes[0] : 0;
+        switch (d->kind) {
+        case MOVE_GATHER: case MOVE_GATHERV:
+            return map_rc(mi355x_gatherv_ddt(e, sv, sb0, rcv.base, rcv.d, rcv.cnt, rdis, root, NULL));
+        case MOVE_SCATTER: case MOVE_SCATTERV:
+            return map_rc(mi355x_scatterv_ddt(e, sv, sbytes, soff, rcv.base + rcv.udisp[0], rcv.d, rcv.cnt[0], root, NULL));
+        case MOVE_ALLGATHERV: return map_rc(mi355x_allgatherv_ddt(e, sv, sb0, rcv.base, rcv.d, rcv.cnt, rdis, NULL));
+        default: return map_rc(mi355x_alltoallv_ddt(e, sv, sbytes, soff, rcv.base, rcv.d, rcv.cnt, rdis, NULL));
+        }
+    }
     switch (d->kind) {
     case MOVE_GATHER: erc = mi355x_gather(e, sv, rv, ssig ? sbytes[0] : rbytes[me], root, NULL); break;
     case MOVE_GATHERV: erc = mi355x_gatherv(e, sv, ssig ? sbytes[0] : 0, rv, rbytes, roff, root, NULL); break;

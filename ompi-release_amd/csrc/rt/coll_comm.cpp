@@ -483,6 +483,7 @@ int mi355x_comm_get(const mi355x_comm_t *c, int knob, long *value)
     case MI355X_KNOB_RCACHE_EVICTIONS: *value = (long)c->rcache_evictions; break;
     case MI355X_KNOB_NB_ORDER: *value = c->nb_order; break;
     case MI355X_KNOB_SCAN_PART_MIN_BYTES: *value = (long)c->scan_part_min; break;
+    case MI355X_KNOB_MOVE_FUSED: *value = (long)c->move_fused; break;
     default: return set_error(MI355X_ERR_ARG, "unknown knob %d", knob);
     }
     return MI355X_SUCCESS;

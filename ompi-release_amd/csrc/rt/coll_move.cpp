@@ -21,13 +21,54 @@
 
 #include "comm_internal.hpp"
 #include "coll_comm_int.hpp"
+#include "ddt_internal.hpp"
 
 namespace mi355x {
 
-static int copy_segments(MultiCopyArgs &m, hipStream_t s)
+// The pull.  Plain bytes: k_multicopy.  With a receive layout (the _ddt forms) the segments' bytes
+// are packed streams of `rddt`, each unpacked from where it lies -- the owner's memory -- into the
+// layout at its destination (ddt_unpack_segments): no dense receive view, no second pass.
+static int copy_segments(mi355x_comm *c, MultiCopyArgs &m, hipStream_t s, const mi355x_ddt *rddt = nullptr)
 {
     if (m.nseg == 0) return MI355X_SUCCESS;
-    return launch_multicopy(m, s);
+    if (!rddt) return launch_multicopy(m, s);
+    c->move_fused++;
+    return ddt_unpack_segments(rddt, m.src, m.dst, m.len, m.nseg, s);
+}
+
+// The receive side of a _ddt form as the impls take it.  A layout with gaps stays (d); a NULL one,
+// or one whose instances leave no gap (ddt_contiguous for the largest count), becomes the plain
+// form's byte counts and displacements, so such a call IS the plain call.
+struct RecvSide {
+    const mi355x_ddt *d;
+    const size_t *counts, *displs;
+    int64_t first = 0;  // a gap-free layout's first byte, from the piece's base (in displs already)
+    std::vector<size_t> bytes;
+    RecvSide(const mi355x_ddt *rddt, int n, const size_t *cnt, const size_t *dsp) : d(rddt), counts(cnt), displs(dsp)
+    {
+        if (!rddt || !cnt) return;
+        size_t most = 0;
+        for (int q = 0; q < n; ++q) most = std::max(most, cnt[q]);
+        if (!ddt_contiguous(rddt, most, &first)) {
+            first = 0;
+            return;
+        }
+        const size_t sz = mi355x_ddt_size(rddt);
+        bytes.resize(2 * (size_t)n);
+        for (int q = 0; q < n; ++q) {
+            bytes[(size_t)q] = cnt[q] * sz;
+            bytes[(size_t)(n + q)] = (dsp ? dsp[q] : 0) + (size_t)first;
+        }
+        counts = bytes.data();
+        if (dsp) displs = bytes.data() + n;
+        d = nullptr;
+    }
+};
+
+// bytes piece q of a receive side holds: rcounts are bytes, or with a layout instances of it
+static size_t piece_bytes(const mi355x_ddt *rddt, size_t count)
+{
+    return rddt ? count * mi355x_ddt_size(rddt) : count;
 }
 
 static void add_seg(MultiCopyArgs &m, const void *src, void *dst, size_t len)
@@ -49,12 +90,17 @@ static int check_comm(mi355x_comm *c, int root)
 
 // MPI_Gatherv: the root pulls rank q's sbytes into rbuf + displs[q] (at most rcounts[q] bytes).
 // sbuf NULL at the root = MPI_IN_PLACE (its block is already in rbuf).
+// rddt (every impl below): NULL, or the receive layout -- rcounts are then instances of it, displs
+// still bytes, and the pull unpacks (copy_segments); everything up to the launch is the plain form's,
+// so a rank may call this form while its peers call the plain one.
 static int gatherv_impl(mi355x_comm *c, const void *sbuf, size_t sbytes, void *rbuf, const size_t *rcounts,
-                        const size_t *displs, int root, void *stream)
+                        const size_t *displs, int root, void *stream, const mi355x_ddt *rddt = nullptr)
 {
     int rc = check_comm(c, root);
     if (rc) return rc;
     const bool am_root = c->rank == root;
+    if (!am_root) rddt = nullptr;  // (no receive side)
+    if (rddt && !sbuf) return set_error(MI355X_ERR_UNSUPPORTED, "gatherv: MPI_IN_PLACE with a receive layout");
     if (am_root && (!rcounts || !displs)) return set_error(MI355X_ERR_ARG, "gatherv: counts at the root are NULL");
     if (!am_root && !sbuf && sbytes) return set_error(MI355X_ERR_ARG, "MPI_IN_PLACE is only valid at the root");
     hipStream_t s = resolve_stream(stream);
@@ -72,12 +118,12 @@ static int gatherv_impl(mi355x_comm *c, const void *sbuf, size_t sbytes, void *r
         std::memset(&m, 0, sizeof(m));
         for (int q = 0; q < c->size; ++q) {
             const size_t qb = (size_t)c->ctrl->slot[q].varg[0];
-            if (qb > rcounts[q])
+            if (qb > piece_bytes(rddt, rcounts[q]))
                 return set_error(MI355X_ERR_TRUNCATE, "gatherv: rank %d sends %zu bytes, root expects %zu", q, qb,
-                                 rcounts[q]);
+                                 piece_bytes(rddt, rcounts[q]));
             if (qb) add_seg(m, P[0][q], (char *)rbuf + displs[q], qb);
         }
-        rc = copy_segments(m, s);
+        rc = copy_segments(c, m, s, rddt);
         if (rc) return rc;
     }
     return finish(c, s);
@@ -86,7 +132,7 @@ static int gatherv_impl(mi355x_comm *c, const void *sbuf, size_t sbytes, void *r
 // MPI_Scatterv: rank r pulls scounts[r] bytes at root's sbuf + displs[r] (both published by the
 // root) into rbuf (at most rbytes).  rbuf NULL at the root = MPI_IN_PLACE.
 static int scatterv_impl(mi355x_comm *c, const void *sbuf, const size_t *scounts, const size_t *displs, void *rbuf,
-                         size_t rbytes, int root, void *stream)
+                         size_t rbytes, int root, void *stream, const mi355x_ddt *rddt = nullptr)
 {
     int rc = check_comm(c, root);
     if (rc) return rc;
@@ -112,13 +158,13 @@ static int scatterv_impl(mi355x_comm *c, const void *sbuf, const size_t *scounts
     const RankSlot &rs = c->ctrl->slot[root];
     const size_t len = (size_t)rs.varg[c->rank];
     if (rbuf && len) {
-        if (len > rbytes)
+        if (len > piece_bytes(rddt, rbytes))
             return set_error(MI355X_ERR_TRUNCATE, "scatterv: root sends %zu bytes to rank %d, which expects %zu", len,
-                             c->rank, rbytes);
+                             c->rank, piece_bytes(rddt, rbytes));
         MultiCopyArgs m;
         std::memset(&m, 0, sizeof(m));
         add_seg(m, (const char *)P[0][root] + rs.varg[kMaxRanks + c->rank], rbuf, len);
-        rc = copy_segments(m, s);
+        rc = copy_segments(c, m, s, rddt);
         if (rc) return rc;
     }
     return finish(c, s);
@@ -127,20 +173,21 @@ static int scatterv_impl(mi355x_comm *c, const void *sbuf, const size_t *scounts
 // MPI_Allgatherv: every rank pulls rank q's block (rcounts[q] bytes) into rbuf + displs[q].
 // sbuf NULL = MPI_IN_PLACE (the rank's block is at rbuf + displs[rank]).
 static int allgatherv_impl(mi355x_comm *c, const void *sbuf, size_t sbytes, void *rbuf, const size_t *rcounts,
-                           const size_t *displs, void *stream)
+                           const size_t *displs, void *stream, const mi355x_ddt *rddt = nullptr)
 {
     int rc = check_comm(c, 0);
     if (rc) return rc;
     if (!rcounts || !displs) return set_error(MI355X_ERR_ARG, "allgatherv: counts are NULL");
+    if (rddt && !sbuf) return set_error(MI355X_ERR_UNSUPPORTED, "allgatherv: MPI_IN_PLACE with a receive layout");
     hipStream_t s = resolve_stream(stream);
     CallStream call_stream(c, s);
     MI_HIP(hipStreamSynchronize(s));
     const int me = c->rank;
     const void *src = sbuf ? sbuf : (const char *)rbuf + displs[me];
     const size_t mybytes = sbuf ? sbytes : rcounts[me];
-    if (mybytes > rcounts[me])
+    if (mybytes > piece_bytes(rddt, rcounts[me]))
         return set_error(MI355X_ERR_TRUNCATE, "allgatherv: rank %d sends %zu bytes, %zu expected", me, mybytes,
-                         rcounts[me]);
+                         piece_bytes(rddt, rcounts[me]));
     const void *mine[1] = {mybytes ? src : nullptr};
     const uint64_t sig[4] = {22, 0, 0, 0};
     std::vector<std::vector<void *>> P;
@@ -150,8 +197,9 @@ static int allgatherv_impl(mi355x_comm *c, const void *sbuf, size_t sbytes, void
     MultiCopyArgs m;
     std::memset(&m, 0, sizeof(m));
     for (int q = 0; q < c->size; ++q)
-        if (rcounts[q] && P[0][q]) add_seg(m, P[0][q], (char *)rbuf + displs[q], q == me ? mybytes : rcounts[q]);
-    rc = copy_segments(m, s);
+        if (rcounts[q] && P[0][q])
+            add_seg(m, P[0][q], (char *)rbuf + displs[q], q == me ? mybytes : piece_bytes(rddt, rcounts[q]));
+    rc = copy_segments(c, m, s, rddt);
     if (rc) return rc;
     return finish(c, s);
 }
@@ -160,12 +208,13 @@ static int allgatherv_impl(mi355x_comm *c, const void *sbuf, size_t sbytes, void
 // (published by q) into rbuf + rdispls[q] (at most rcounts[q]).  sbuf NULL = MPI_IN_PLACE: the
 // data to send is rbuf laid out by rcounts / rdispls, snapshotted into scratch first.
 static int alltoallv_impl(mi355x_comm *c, const void *sbuf, const size_t *scounts, const size_t *sdispls, void *rbuf,
-                          const size_t *rcounts, const size_t *rdispls, void *stream)
+                          const size_t *rcounts, const size_t *rdispls, void *stream, const mi355x_ddt *rddt = nullptr)
 {
     int rc = check_comm(c, 0);
     if (rc) return rc;
     if (!rcounts || !rdispls || (sbuf && (!scounts || !sdispls)))
         return set_error(MI355X_ERR_ARG, "alltoallv: counts are NULL");
+    if (rddt && !sbuf) return set_error(MI355X_ERR_UNSUPPORTED, "alltoallv: MPI_IN_PLACE with a receive layout");
     hipStream_t s = resolve_stream(stream);
     CallStream call_stream(c, s);
     const int n = c->size, me = c->rank;
@@ -201,12 +250,12 @@ static int alltoallv_impl(mi355x_comm *c, const void *sbuf, const size_t *scount
         const int q = (me + k) % n;   // own block first, then the peers in ring order
         const RankSlot &qs = c->ctrl->slot[q];
         const size_t len = (size_t)qs.varg[me];
-        if (len > rcounts[q])
+        if (len > piece_bytes(rddt, rcounts[q]))
             return set_error(MI355X_ERR_TRUNCATE, "alltoallv: rank %d sends %zu bytes to rank %d, which expects %zu",
-                             q, len, me, rcounts[q]);
+                             q, len, me, piece_bytes(rddt, rcounts[q]));
         if (len) add_seg(m, (const char *)P[0][q] + qs.varg[kMaxRanks + me], (char *)rbuf + rdispls[q], len);
     }
-    rc = copy_segments(m, s);
+    rc = copy_segments(c, m, s, rddt);
     if (rc) return rc;
     return finish(c, s);
 }
@@ -276,13 +325,13 @@ static int scan_part(mi355x_comm *c, const void *in, void *rbuf, size_t count, i
             scan_part_plan(count, n, q, me, &qo, &ql, &slot);
             if (ql == 0) continue;
             if (m.nseg == kMaxSegs) {  // (more owners than one launch holds: split the pull)
-                rc = copy_segments(m, s);
+                rc = copy_segments(c, m, s);
                 if (rc) return rc;
                 std::memset(&m, 0, sizeof(m));
             }
             add_seg(m, (const char *)P[1][q] + slot * esz, (char *)rbuf + qo * esz, ql * esz);
         }
-        rc = copy_segments(m, s);
+        rc = copy_segments(c, m, s);
         if (rc) return rc;
     }
     return finish(c, s);  // the owners keep their scratch until everybody has pulled
@@ -333,7 +382,7 @@ static int scan_impl(mi355x_comm *c, const void *sbuf, void *rbuf, size_t count,
         MultiCopyArgs m;
         std::memset(&m, 0, sizeof(m));
         add_seg(m, P[0][0], target, count * esz);
-        rc = copy_segments(m, s);
+        rc = copy_segments(c, m, s);
         if (rc) return rc;
     } else if (last > 0) {
         Program pr;
@@ -421,6 +470,50 @@ int mi355x_alltoallv(mi355x_comm_t *c, const void *sbuf, const size_t *scounts, 
     drain(c);
     CallGate gate(c);
     return alltoallv_impl(c, sbuf, scounts, sdispls, rbuf, rcounts, rdispls, stream);
+}
+
+int mi355x_gatherv_ddt(mi355x_comm_t *c, const void *sbuf, size_t sbytes, void *rbuf, const mi355x_ddt_t *rddt,
+                       const size_t *rcounts, const size_t *rdispls, int root, void *stream)
+{
+    if (!c) return set_error(MI355X_ERR_ARG, "comm is NULL");
+    const RecvSide r(rddt, c->size, c->rank == root ? rcounts : nullptr, rdispls);
+    DeviceGuard dg(c->device);
+    drain(c);
+    CallGate gate(c);
+    return gatherv_impl(c, sbuf, sbytes, rbuf, r.counts, r.displs, root, stream, r.d);
+}
+
+int mi355x_scatterv_ddt(mi355x_comm_t *c, const void *sbuf, const size_t *scounts, const size_t *sdispls, void *rbuf,
+                        const mi355x_ddt_t *rddt, size_t rcount, int root, void *stream)
+{
+    if (!c) return set_error(MI355X_ERR_ARG, "comm is NULL");
+    const RecvSide r(rddt, 1, &rcount, nullptr);
+    DeviceGuard dg(c->device);
+    drain(c);
+    CallGate gate(c);
+    return scatterv_impl(c, sbuf, scounts, sdispls, rbuf ? (char *)rbuf + r.first : rbuf, r.counts[0], root, stream, r.d);
+}
+
+int mi355x_allgatherv_ddt(mi355x_comm_t *c, const void *sbuf, size_t sbytes, void *rbuf, const mi355x_ddt_t *rddt,
+                          const size_t *rcounts, const size_t *rdispls, void *stream)
+{
+    if (!c) return set_error(MI355X_ERR_ARG, "comm is NULL");
+    const RecvSide r(rddt, c->size, rcounts, rdispls);
+    DeviceGuard dg(c->device);
+    drain(c);
+    CallGate gate(c);
+    return allgatherv_impl(c, sbuf, sbytes, rbuf, r.counts, r.displs, stream, r.d);
+}
+
+int mi355x_alltoallv_ddt(mi355x_comm_t *c, const void *sbuf, const size_t *scounts, const size_t *sdispls, void *rbuf,
+                         const mi355x_ddt_t *rddt, const size_t *rcounts, const size_t *rdispls, void *stream)
+{
+    if (!c) return set_error(MI355X_ERR_ARG, "comm is NULL");
+    const RecvSide r(rddt, c->size, rcounts, rdispls);
+    DeviceGuard dg(c->device);
+    drain(c);
+    CallGate gate(c);
+    return alltoallv_impl(c, sbuf, scounts, sdispls, rbuf, r.counts, r.displs, stream, r.d);
 }
 
 int mi355x_alltoall(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, void *stream)

@@ -415,6 +415,7 @@ struct mi355x_comm {
     int pipe_entry = -1;                          // my registration in that token's holder list while held
     uint64_t pipe_refused = 0;                    // calls that fell back because a token was taken
     uint64_t pipe_calls = 0;                      // allreduces served by the pipelined flow
+    uint64_t move_fused = 0;                      // movement calls whose pull unpacked into a receive layout
     // finish() by device-written completion words (see RankSlot::done): the control segment
     // registered with HIP (hipHostRegister) and its device address; 0 = stream sync + barrier
     // MI355X_LAT_PROFILE=1: host time of the small-message allreduce's steps (entry -> input sync

@@ -222,17 +222,9 @@ size_t mi355x_ddt_size(const mi355x_ddt_t *d) { return d ? (size_t)(d->nblk * bl
 int64_t mi355x_ddt_extent(const mi355x_ddt_t *d) { return d ? d->extent : 0; }
 int mi355x_ddt_nruns(const mi355x_ddt_t *d) { return d ? (int)d->disp.size() : 0; }
 
-static int ddt_move(const mi355x_ddt_t *d, bool pack, size_t count, void *mem, size_t pos, void *packed,
-                    size_t bytes, uint32_t *checksum, void *stream)
+// the kernels' view of an uploaded layout
+static DdtDev dev_view(const mi355x_ddt *d)
 {
-    if (!d || (bytes && (!mem || !packed))) return set_error(MI355X_ERR_ARG, "bad pack arguments");
-    const int64_t inst = d->nblk * blk_bytes(d);
-    if ((int64_t)(pos + bytes) > (int64_t)count * inst) return set_error(MI355X_ERR_ARG, "window past the message");
-    if (checksum) *checksum = 0;
-    if (bytes == 0 || inst == 0) return MI355X_SUCCESS;
-    hipStream_t s = resolve_stream(stream);
-    int rc0 = upload(const_cast<mi355x_ddt *>(d));
-    if (rc0) return rc0;
     DdtDev dv;
     dv.disp = d->ddisp;
     dv.len = d->dlen;
@@ -244,9 +236,24 @@ static int ddt_move(const mi355x_ddt_t *d, bool pack, size_t count, void *mem, s
     dv.stride = d->stride;
     dv.extent = d->extent;
     dv.blk_bytes = blk_bytes(d);
-    dv.inst_bytes = inst;
+    dv.inst_bytes = d->nblk * dv.blk_bytes;
     dv.run_bits = d->run_bits;
     dv.max_len = d->max_len;
+    return dv;
+}
+
+static int ddt_move(const mi355x_ddt_t *d, bool pack, size_t count, void *mem, size_t pos, void *packed,
+                    size_t bytes, uint32_t *checksum, void *stream)
+{
+    if (!d || (bytes && (!mem || !packed))) return set_error(MI355X_ERR_ARG, "bad pack arguments");
+    const int64_t inst = d->nblk * blk_bytes(d);
+    if ((int64_t)(pos + bytes) > (int64_t)count * inst) return set_error(MI355X_ERR_ARG, "window past the message");
+    if (checksum) *checksum = 0;
+    if (bytes == 0 || inst == 0) return MI355X_SUCCESS;
+    hipStream_t s = resolve_stream(stream);
+    int rc0 = upload(const_cast<mi355x_ddt *>(d));
+    if (rc0) return rc0;
+    const DdtDev dv = dev_view(d);
     unsigned h = 0;
     unsigned *sum = checksum ? &h : nullptr;  // the launchers wait for the kernel when asked for one
     int rc = 1;
@@ -270,6 +277,31 @@ bool ddt_contiguous(const mi355x_ddt *d, size_t count, int64_t *first)
     *first = d->disp[0];
     if (d->nblk > 1 && d->stride != len) return false;
     return count <= 1 || d->extent == d->nblk * len;
+}
+
+int ddt_unpack_segments(const mi355x_ddt *d, const void *const *src, void *const *mem, const size_t *len, int nseg,
+                        hipStream_t s)
+{
+    if (!d || nseg < 0 || nseg > kRowsMaxSegs) return set_error(MI355X_ERR_ARG, "bad unpack segments");
+    if (nseg == 0 || d->nblk * blk_bytes(d) == 0) return MI355X_SUCCESS;
+    int rc = upload(const_cast<mi355x_ddt *>(d));
+    if (rc) return rc;
+    const DdtDev dv = dev_view(d);
+    RowSeg segs[kRowsMaxSegs];
+    for (int i = 0; i < nseg; ++i) segs[i] = RowSeg{src[i], mem[i], len[i]};
+    const bool row = d->disp.size() == 1;
+    rc = row ? launch_ddt_rows_multi(dv, d->disp[0], d->len[0], segs, nseg, s) : 1;
+    if (rc != 1) return rc;
+    // several runs per block (the unit / runs / general kernels), or a row layout the one launch
+    // does not take: piece by piece, as mi355x_unpack would, still straight from the source
+    for (int i = 0; i < nseg; ++i) {
+        if (len[i] == 0 || src[i] == mem[i]) continue;
+        void *pk = const_cast<void *>(src[i]);
+        rc = row ? launch_ddt_rows(dv, 1, d->disp[0], d->len[0], false, mem[i], pk, 0, (int64_t)len[i], nullptr, s) : 1;
+        if (rc == 1) rc = launch_ddt(dv, false, mem[i], pk, 0, (int64_t)len[i], nullptr, s);
+        if (rc) return rc;
+    }
+    return MI355X_SUCCESS;
 }
 } // namespace mi355x
 

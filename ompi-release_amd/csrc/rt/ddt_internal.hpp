@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "ddt_rows_plan.hpp"
+
 struct mi355x_ddt;
 
 namespace mi355x {
@@ -47,5 +49,16 @@ int launch_ddt(const DdtDev &d, bool pack, void *mem, void *packed, int64_t pos,
 // address and length allows); returns 1 when it does not apply
 int launch_ddt_rows(const DdtDev &d, int nruns_host, int64_t run_disp, int64_t run_len, bool pack, void *mem,
                     void *packed, int64_t pos, int64_t bytes, unsigned *csum, hipStream_t s);
+// the row kernel's unpack of several packed pieces (each from position 0 of its own stream) into the
+// same one-run layout in one launch (plan_rows_multi, ddt_rows_plan.hpp); returns 1 when it does
+// not apply
+int launch_ddt_rows_multi(const DdtDev &d, int64_t run_disp, int64_t run_len, const RowSeg *segs, int nseg,
+                          hipStream_t s);
+// the pull of a movement collective into a receive layout (coll_move.cpp): piece i = len[i] packed
+// bytes at src[i], which may be a peer's mapped memory, unpacked into d laid at mem[i].  A row
+// layout takes one launch; any other goes piece by piece through launch_ddt (not yet one launch).
+// Nothing is waited for.
+int ddt_unpack_segments(const mi355x_ddt *d, const void *const *src, void *const *mem, const size_t *len, int nseg,
+                        hipStream_t s);
 
 } // namespace mi355x

@@ -15,8 +15,11 @@
 // stream's native 32-bit words (opal_uicsum_partial, opal/util/crc.c:921) -- additive over
 // windows, so per-fragment sums add up to the whole-message convertor checksum.
 #include <algorithm>
+#include <cstring>
 
+#include "coll_internal.hpp"
 #include "ddt_internal.hpp"
+#include "ddt_rows_plan.hpp"
 #include "rt_internal.hpp"
 #include "stream_core.hpp"
 
@@ -255,29 +258,6 @@ __global__ __launch_bounds__(1024) void k_ddt_rows(RowArgs a, CsumSink csum)
     if constexpr (CSUM) block_sum_store(acc, csum);
 }
 
-// largest slot index the 32-bit row / unit kernels take: their grid-stride and last-block index
-// arithmetic (at most 2^22 slots past the end) must not wrap
-constexpr int64_t kSlot32Max = ((int64_t)1 << 32) - ((int64_t)1 << 22);
-
-// the slot width the row kernel can use (0: it does not apply): one run per block, and every
-// address, length and window a multiple of W; slot / row counts in 32 bits
-static int rows_width(const DdtDev &d, int nruns_host, int64_t run_disp, int64_t run_len, const void *mem,
-                      const void *packed, int64_t pos, int64_t bytes)
-{
-    if (nruns_host != 1 || run_len <= 0) return 0;
-    const uint64_t bits = (uint64_t)run_len | ((uintptr_t)mem + (uint64_t)run_disp) | (uint64_t)d.stride |
-                          (uint64_t)d.extent | (uintptr_t)packed | (uint64_t)pos | (uint64_t)bytes;
-    int w = 16;
-    while (w > 1 && (bits & (uint64_t)(w - 1))) w >>= 1;
-    const int64_t last_slot = (pos + bytes) / w;
-    const int64_t rows = last_slot / (run_len / w) + 1;
-    // 32-bit slot arithmetic, with headroom for the last block's (tpb x U)-slot stride
-    if (last_slot >= kSlot32Max || rows >= ((int64_t)1 << 32) || d.nblk >= ((int64_t)1 << 32) ||
-        (run_len / w) >= ((int64_t)1 << 32))
-        return 0;
-    return w;
-}
-
 DdtTune &ddt_tune()
 {
     static DdtTune t;
@@ -405,7 +385,7 @@ int launch_ddt_rows(const DdtDev &d, int nruns_host, int64_t run_disp, int64_t r
                     void *packed, int64_t pos, int64_t bytes, unsigned *csum, hipStream_t s)
 {
     const int mode = ddt_tune().rows;
-    const int w = mode > 0 ? rows_width(d, nruns_host, run_disp, run_len, mem, packed, pos, bytes) : 0;
+    const int w = mode > 0 ? rows_width(d.stride, d.extent, d.nblk, nruns_host, run_disp, run_len, mem, packed, pos, bytes) : 0;
     if (w == 0 || (w < 16 && mode < 2)) return 1;
     RowArgs a;
     a.mem = static_cast<char *>(mem);
@@ -446,6 +426,109 @@ int launch_ddt_rows(const DdtDev &d, int nruns_host, int64_t run_disp, int64_t r
     }
     MI_HIP(hipGetLastError());
     return part.finish(csum, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Multi-segment row unpack: the pull of a movement collective into a derived receive datatype.
+// Up to kRowsMaxSegs packed pieces -- one per peer, each read where it lies, in the peer's mapped
+// memory -- go into the same row layout at their own memory bases in ONE launch, so every xGMI
+// link runs at once and the bytes are read once and written once (no dense receive view, no second
+// pass).  The pieces share the layout, the two divisions and the slot width; blocks are dealt to
+// them by bytes (plan_rows_multi, first_block[] by value), a block finds its piece from that table
+// as k_multicopy's do and runs k_ddt_rows' per-slot body (rows_pass) on it, looping when the piece
+// got fewer blocks than it has (tpb x U)-slot passes.  Only the packed side may be remote, and it
+// is only read; pieces may interleave in memory (columns resized to one element's extent share
+// cache lines): their bytes are disjoint, so they need no order between them.
+static_assert(kRowsMaxSegs == kMaxSegs, "one piece per rank, as k_multicopy's segments");
+struct MultiRowArgs {
+    const char *packed[kRowsMaxSegs];
+    char *mem[kRowsMaxSegs];
+    uint32_t nslots[kRowsMaxSegs];
+    unsigned first_block[kRowsMaxSegs + 1];
+    int nseg;
+    int64_t disp, stride, extent;
+    FastDiv per_row, per_inst;
+};
+
+template <int NTM, int U, int W>
+__global__ __launch_bounds__(1024) void k_ddt_rows_multi(MultiRowArgs m)
+{
+    // find this block's piece (<= 64 pieces, uniform per block)
+    int sgi = 0;
+    while (sgi + 1 < m.nseg && blockIdx.x >= m.first_block[sgi + 1]) ++sgi;
+    const unsigned nb = m.first_block[sgi + 1] - m.first_block[sgi];
+    const unsigned b = blockIdx.x - m.first_block[sgi];
+    RowArgs a;
+    a.mem = m.mem[sgi];
+    a.packed = const_cast<char *>(m.packed[sgi]);  // (the unpack only reads it)
+    a.disp = m.disp;
+    a.stride = m.stride;
+    a.extent = m.extent;
+    a.per_row = m.per_row;
+    a.per_inst = m.per_inst;
+    a.first = 0;
+    a.nslots = m.nslots[sgi];
+    const uint32_t tpb = blockDim.x;
+    const uint64_t per = (uint64_t)tpb * U;
+    for (uint64_t base = (uint64_t)b * per + threadIdx.x; base < a.nslots; base += (uint64_t)nb * per)
+        (void)rows_pass<false, false, NTM, U, W>(a, (uint32_t)base, tpb);
+}
+
+template <int NTM, int U, int W>
+static void launch_rows_multi_k(const MultiRowArgs &m, unsigned tpb, unsigned blocks, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_ddt_rows_multi<NTM, U, W>), dim3(blocks), dim3(tpb), 0, s, m);
+}
+
+template <int NTM>
+static void launch_rows_multi_w(int w, int unroll, const MultiRowArgs &m, unsigned tpb, unsigned blocks, hipStream_t s)
+{
+    switch (w) {
+    case 16:
+        if (unroll == 2) launch_rows_multi_k<NTM, 2, 16>(m, tpb, blocks, s);
+        else if (unroll == 8) launch_rows_multi_k<NTM, 8, 16>(m, tpb, blocks, s);
+        else launch_rows_multi_k<NTM, 4, 16>(m, tpb, blocks, s);
+        break;
+    case 8: launch_rows_multi_k<NTM, kNarrowUnroll, 8>(m, tpb, blocks, s); break;
+    case 4: launch_rows_multi_k<NTM, kNarrowUnroll, 4>(m, tpb, blocks, s); break;
+    case 2: launch_rows_multi_k<NTM, kNarrowUnroll, 2>(m, tpb, blocks, s); break;
+    default: launch_rows_multi_k<NTM, kNarrowUnroll, 1>(m, tpb, blocks, s); break;
+    }
+}
+
+int launch_ddt_rows_multi(const DdtDev &d, int64_t run_disp, int64_t run_len, const RowSeg *segs, int nseg,
+                          hipStream_t s)
+{
+    const DdtTune &t = ddt_tune();
+    if (t.rows <= 0) return 1;
+    int unroll = t.unroll_unpack;
+    if (unroll != 2 && unroll != 8) unroll = 4;
+    const unsigned tpb = (t.threads == 256 || t.threads == 512) ? (unsigned)t.threads : 1024u;
+    const size_t cap = (size_t)coll_tune().blocks_per_cu * (size_t)device_cu_count();
+    const RowsMultiPlan p = plan_rows_multi(d.stride, d.extent, d.nblk, run_disp, run_len, segs, nseg, tpb * (unsigned)unroll,
+                                            tpb * (unsigned)kNarrowUnroll, cap);
+    if (p.w == 0 || (p.w < 16 && t.rows < 2)) return 1;
+    if (p.nseg == 0) return MI355X_SUCCESS;
+    MultiRowArgs m;
+    std::memset(&m, 0, sizeof(m));
+    for (int i = 0; i < p.nseg; ++i) {
+        const RowSeg &g = segs[p.seg[i]];
+        m.packed[i] = static_cast<const char *>(g.packed);
+        m.mem[i] = static_cast<char *>(g.mem);
+        m.nslots[i] = (uint32_t)(g.len / (size_t)p.w);
+    }
+    for (int i = 0; i <= p.nseg; ++i) m.first_block[i] = p.first_block[i];
+    m.nseg = p.nseg;
+    m.disp = run_disp;
+    m.stride = d.stride;
+    m.extent = d.extent;
+    m.per_row = make_fastdiv((uint32_t)(run_len / p.w));
+    m.per_inst = make_fastdiv((uint32_t)d.nblk);
+    // the load flavour and the non-temporal rule of k_multicopy, whose place this launch takes
+    if (beyond_mall(2 * p.total)) launch_rows_multi_w<3>(p.w, unroll, m, tpb, p.first_block[p.nseg], s);
+    else launch_rows_multi_w<0>(p.w, unroll, m, tpb, p.first_block[p.nseg], s);
+    MI_HIP(hipGetLastError());
+    return MI355X_SUCCESS;
 }
 
 // ---------------------------------------------------------------------------------------------
