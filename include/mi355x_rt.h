@@ -271,9 +271,22 @@ enum mi355x_knob {
                                            nonblocking, take the partitioned flow (see mi355x_scan); 0 = never.
                                            The results do not depend on it.  Set only while no nonblocking call
                                            is pending. */
-    MI355X_KNOB_MOVE_FUSED = 46          /* (read-only) movement calls of this communicator whose pull went
+    MI355X_KNOB_MOVE_FUSED = 46,         /* (read-only) movement calls of this communicator whose pull went
                                            through a receive layout (the _ddt forms below): this rank unpacked
                                            its peers' bytes straight from their memory */
+    MI355X_KNOB_MOVE_SEND_DIRECT = 47,   /* (read-only) movement calls in which this rank published a send layout
+                                           (the _ddt2 forms below) and packed nothing: its peers read the rows
+                                           where the application left them */
+    MI355X_KNOB_MOVE_SEND_MIN_RUN = 48   /* (per communicator; the ranks need not agree -- the choice is the
+                                           sender's alone and a receiver serves either record; env
+                                           MI355X_MOVE_SEND_MIN_RUN at creation) the shortest run, in bytes, of a
+                                           send layout this rank publishes directly instead of packing; 0 = never.
+                                           The results do not depend on it.  Default 16, the shortest run swept:
+                                           with the ranks sharing ONE GPU an alltoall of 64 MiB per rank out of
+                                           runs of 16, 64, 256 and 4096 bytes at stride 2 x run took 0.51 .. 0.74
+                                           of pack + plain call at 2, 4 and 8 ranks ("Pulling out of
+                                           a send layout").  What a strided read of short runs costs across xGMI
+                                           that run cannot show: raise the knob there if it loses. */
 };
 /* cross-device flows (MI355X_KNOB_FLOWS) */
 enum mi355x_flow {
@@ -386,6 +399,37 @@ int mi355x_allgatherv_ddt(mi355x_comm_t *comm, const void *sbuf, size_t sbytes, 
 int mi355x_alltoallv_ddt(mi355x_comm_t *comm, const void *sbuf, const size_t *scounts, const size_t *sdispls,
                          void *rbuf, const mi355x_ddt_t *rddt, const size_t *rcounts, const size_t *rdispls,
                          void *stream);
+/* The same four calls with a layout on the send side too: what this rank sends is NOT packed.  The
+ * rank publishes sbuf itself and, beside its byte counts, the rows of `sddt`; each receiver reads
+ * them where they lie and writes them through its own rddt (or as dense bytes) in one launch, the
+ * two-ended row gather.  Send counts (gatherv / allgatherv: scount) are INSTANCES of sddt, send
+ * displacements BYTES.  The truncation rule, and every step before the pull, are the plain forms',
+ * so in one collective the _ddt2, _ddt and plain forms meet: a peer that sends dense bytes publishes
+ * the "dense" record.  sddt NULL: the send counts are bytes and the call is exactly the _ddt form;
+ * a layout without gaps is that call too.  Any other sddt must pass the rule of
+ * mi355x_move_send_direct_ok -- one run per block; not MPI_IN_PLACE; no byte below sbuf; every
+ * piece below 2^32 - 2^22 packed bytes; the run at least MI355X_KNOB_MOVE_SEND_MIN_RUN bytes, and
+ * that knob not 0 -- else the call returns MI355X_ERR_UNSUPPORTED before the rank meets its peers
+ * and the caller packs as before.  Every byte the layout reaches must lie in the allocation that
+ * contains sbuf (MI355X_ERR_ARG otherwise).  A receive layout with several runs per block takes two
+ * passes (the rows gathered into the communicator's scratch, then unpacked).  sddt is not read on a
+ * rank that sends nothing significant (scatterv off the root).  Calls in which this rank published
+ * a layout are counted by MI355X_KNOB_MOVE_SEND_DIRECT; MI355X_KNOB_MOVE_FUSED keeps counting the
+ * pulls into a receive layout. */
+int mi355x_gatherv_ddt2(mi355x_comm_t *comm, const void *sbuf, const mi355x_ddt_t *sddt, size_t scount, void *rbuf,
+                        const mi355x_ddt_t *rddt, const size_t *rcounts, const size_t *rdispls, int root, void *stream);
+int mi355x_scatterv_ddt2(mi355x_comm_t *comm, const void *sbuf, const mi355x_ddt_t *sddt, const size_t *scounts,
+                         const size_t *sdispls, void *rbuf, const mi355x_ddt_t *rddt, size_t rcount, int root,
+                         void *stream);
+int mi355x_allgatherv_ddt2(mi355x_comm_t *comm, const void *sbuf, const mi355x_ddt_t *sddt, size_t scount, void *rbuf,
+                           const mi355x_ddt_t *rddt, const size_t *rcounts, const size_t *rdispls, void *stream);
+int mi355x_alltoallv_ddt2(mi355x_comm_t *comm, const void *sbuf, const mi355x_ddt_t *sddt, const size_t *scounts,
+                          const size_t *sdispls, void *rbuf, const mi355x_ddt_t *rddt, const size_t *rcounts,
+                          const size_t *rdispls, void *stream);
+/* the rule above for n pieces of scounts[] instances of sddt, not in place, under the communicator's
+ * MOVE_SEND_MIN_RUN: 1 the layout would be published, 0 it would not (the caller packs; a layout
+ * without gaps is the plain call), or a negative status.  Host only. */
+int mi355x_move_send_direct_ok(const mi355x_comm_t *comm, const mi355x_ddt_t *sddt, const size_t *scounts, int n);
 int mi355x_scan(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t count, int type, int op, void *stream);
 int mi355x_exscan(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t count, int type, int op, void *stream);
 /* The partitioned scan flow's layout (host only, no GPU needed): owner q's block of a count-element

@@ -179,6 +179,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         "mi355x_scatterv_ddt": (i, [vp, vp, c.POINTER(sz), c.POINTER(sz), vp, vp, sz, i, vp]),
         "mi355x_allgatherv_ddt": (i, [vp, vp, sz, vp, vp, c.POINTER(sz), c.POINTER(sz), vp]),
         "mi355x_alltoallv_ddt": (i, [vp, vp, c.POINTER(sz), c.POINTER(sz), vp, vp, c.POINTER(sz), c.POINTER(sz), vp]),
+        "mi355x_gatherv_ddt2": (i, [vp, vp, vp, sz, vp, vp, c.POINTER(sz), c.POINTER(sz), i, vp]),
+        "mi355x_scatterv_ddt2": (i, [vp, vp, vp, c.POINTER(sz), c.POINTER(sz), vp, vp, sz, i, vp]),
+        "mi355x_allgatherv_ddt2": (i, [vp, vp, vp, sz, vp, vp, c.POINTER(sz), c.POINTER(sz), vp]),
+        "mi355x_alltoallv_ddt2": (i, [vp, vp, vp, c.POINTER(sz), c.POINTER(sz), vp, vp, c.POINTER(sz), c.POINTER(sz), vp]),
+        "mi355x_move_send_direct_ok": (i, [vp, vp, c.POINTER(sz), i]),
         "mi355x_scan": (i, [vp, vp, vp, sz, i, i, vp]),
         "mi355x_exscan": (i, [vp, vp, vp, sz, i, i, vp]),
         "mi355x_iscan": (i, [vp, vp, vp, sz, i, i, vp, c.POINTER(vp)]),
@@ -287,7 +292,7 @@ KNOB = {"ALLREDUCE_ALG": 1, "REDUCE_ALG": 2, "REDUCE_SCATTER_ALG": 3, "BLOCKS_PE
         "SVC_OWNER": 33, "SVC_CLAIMS": 34, "SVC_IDLE_US": 35,
         "SVC_SHRINK_US": 36, "SVC_REGROWS": 37, "DEV_SETUP": 38, "SETUP_US": 39, "SELFTEST": 40,
         "PIPE_CALLS": 41, "EXPORT_MISMATCHES": 42, "SELFTEST_REUSED": 43, "NB_ORDER": 44,
-        "SCAN_PART_MIN_BYTES": 45, "MOVE_FUSED": 46}
+        "SCAN_PART_MIN_BYTES": 45, "MOVE_FUSED": 46, "MOVE_SEND_DIRECT": 47, "MOVE_SEND_MIN_RUN": 48}
 # coll/libnbc's algorithms (mi355x_comm_last_algorithm under NB_ORDER = 1, mi355x_nbc_decision)
 NBC_ALG = {"BINOMIAL": 101, "RING": 102, "CHAIN": 103}
 FLOW = {"SVC_LL": 1, "SVC_PULL": 2, "SVC_COPY": 4, "SVC_RS": 8, "PIPE": 16}
@@ -458,6 +463,32 @@ class Comm:
         check(rt().mi355x_alltoallv_ddt(self.h, sbuf, self._sizes(scounts), self._sizes(sdispls), rbuf,
                                         rddt.h if rddt else None, self._sizes(rcounts), self._sizes(rdispls), stream),
               "mi355x_alltoallv_ddt")
+
+    # ---- the same with a layout on the send side too, published instead of packed: send counts in
+    #      instances of sddt (a Ddt, or None: bytes, the _ddt call), send displacements in bytes
+    def gatherv_ddt2(self, sbuf, sddt, scount, rbuf, rddt, rcounts, rdispls, root, stream=None) -> None:
+        check(rt().mi355x_gatherv_ddt2(self.h, sbuf, sddt.h if sddt else None, scount, rbuf, rddt.h if rddt else None,
+                                       self._sizes(rcounts), self._sizes(rdispls), root, stream), "mi355x_gatherv_ddt2")
+
+    def scatterv_ddt2(self, sbuf, sddt, scounts, sdispls, rbuf, rddt, rcount, root, stream=None) -> None:
+        check(rt().mi355x_scatterv_ddt2(self.h, sbuf, sddt.h if sddt else None, self._sizes(scounts), self._sizes(sdispls),
+                                        rbuf, rddt.h if rddt else None, rcount, root, stream), "mi355x_scatterv_ddt2")
+
+    def allgatherv_ddt2(self, sbuf, sddt, scount, rbuf, rddt, rcounts, rdispls, stream=None) -> None:
+        check(rt().mi355x_allgatherv_ddt2(self.h, sbuf, sddt.h if sddt else None, scount, rbuf, rddt.h if rddt else None,
+                                          self._sizes(rcounts), self._sizes(rdispls), stream), "mi355x_allgatherv_ddt2")
+
+    def alltoallv_ddt2(self, sbuf, sddt, scounts, sdispls, rbuf, rddt, rcounts, rdispls, stream=None) -> None:
+        check(rt().mi355x_alltoallv_ddt2(self.h, sbuf, sddt.h if sddt else None, self._sizes(scounts),
+                                         self._sizes(sdispls), rbuf, rddt.h if rddt else None, self._sizes(rcounts),
+                                         self._sizes(rdispls), stream), "mi355x_alltoallv_ddt2")
+
+    def move_send_direct_ok(self, sddt, scounts) -> bool:
+        """mi355x_move_send_direct_ok: would this rank publish sddt for these counts instead of packing it"""
+        rc = rt().mi355x_move_send_direct_ok(self.h, sddt.h, self._sizes(scounts), len(scounts))
+        if rc < 0:
+            check(rc, "mi355x_move_send_direct_ok")
+        return rc == 1
 
     def scan(self, sbuf, rbuf, count, ty, op, stream=None) -> None:
         check(rt().mi355x_scan(self.h, sbuf, rbuf, count, ty, op, stream), "mi355x_scan")

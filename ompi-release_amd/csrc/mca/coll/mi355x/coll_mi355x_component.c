@@ -292,6 +292,7 @@ int mca_coll_mi355x_svc_shrink_us = 100;
 int mca_coll_mi355x_selftest = 1;
 int mca_coll_mi355x_nb_order = 0;
 unsigned long long mca_coll_mi355x_scan_part_min = 0;  /* measured: BASELINE.md, "Partitioned scan" */
+unsigned long long mca_coll_mi355x_move_send_min_run = 16;  /* measured: BASELINE.md, "Pulling out of a send layout" */
 int mca_coll_mi355x_timeout_s = 0;  /* 0: the engine's own (MI355X_TIMEOUT_S, else one day) */
 
 /* 1: the call runs in the engine (a rank with host buffers joins on device copies); 0: it runs in
@@ -539,7 +540,8 @@ typedef struct {
     mi355x_ddt_t *d;          /* NULL: dense, view == base */
     int host;                 /* host memory (a rank joining a call whose peers hold device buffers):
                                  the view is a device staging copy, moved by xstage */
-    int direct;               /* a derived device receive side the engine unpacks into itself: no view */
+    int direct;               /* a derived device side the engine reads or writes through its layout itself:
+                                 no view (the receive side of a _ddt form, the send side of a _ddt2 form) */
     const struct ompi_datatype_t *dt;
     char *view;
     size_t bytes[SIDE_MAX], off[SIDE_MAX], cnt[SIDE_MAX];
@@ -548,7 +550,9 @@ typedef struct {
 
 /* counts/displacements in instances (NULL disps: consecutive pieces of `counts`; NULL counts:
  * every piece `count1` instances).  direct: a derived device layout takes no scratch -- the engine
- * pulls straight into it (sides_engine); the side then has no view.  Returns OMPI_SUCCESS or an error. */
+ * pulls straight into it (1, a receive side) or lets the peers pull straight out of it (2, a send
+ * side, when the engine's rule mi355x_move_send_direct_ok admits the layout); the side then has no
+ * view.  Returns OMPI_SUCCESS or an error. */
 static int side_init(mca_coll_mi355x_module_t *m, side_t *s, int slot, void *buf, const struct ompi_datatype_t *dt,
                      int n, const int *counts, int count1, const int *disps, int direct)
 {
@@ -584,6 +588,7 @@ static int side_init(mca_coll_mi355x_module_t *m, side_t *s, int slot, void *buf
     if (direct && s->d && !s->host) {
         s->direct = 1;
         for (int q = 0; q < n; ++q) s->direct = s->direct && s->udisp[q] >= 0;  /* (the engine's are unsigned) */
+        if (s->direct && direct == 2) s->direct = mi355x_move_send_direct_ok(m->engine, s->d, s->cnt, n) == 1;
         if (s->direct) return OMPI_SUCCESS;
     }
     size_t total = 0;
@@ -1077,26 +1082,55 @@ static int movement_staged(mca_coll_mi355x_module_t *m, const movement_t *d, str
  * `me` (gather(v), allgatherv) or every piece (alltoall(v)) -- the engine's call, the receive side unpacked.
  * A derived receive side in device memory, not in place, has no scratch and no unpack of its own: the
  * engine's _ddt form pulls the peers' bytes straight into the layout (the fixed-count kinds through the
- * v-forms, with the per-piece arrays of side_init).  Every rank still makes the same engine collective --
- * the _ddt and the plain forms meet -- so the path depends on no rank-local layout; only the kernel of
- * this rank's own pull does. */
+ * v-forms, with the per-piece arrays of side_init).  A derived send side in device memory, not in place,
+ * that the engine's rule admits (one run per block, runs of coll_mi355x_move_send_min_run bytes or more)
+ * has no scratch and no pack either: the _ddt2 form publishes the layout and the peers pull out of it.
+ * Every rank still makes the same engine collective -- the _ddt2, the _ddt and the plain forms meet -- so
+ * the path depends on no rank-local layout; only this rank's publication and the kernel of its own pull do. */
 static int sides_engine(mca_coll_mi355x_module_t *m, const movement_t *d, struct ompi_communicator_t *comm)
 {
     const int me = mi355x_comm_rank_of(comm), root = d->root, ssig = d->s.sig, rsig = d->r.sig;
     const int every = d->kind == MOVE_ALLTOALL || d->kind == MOVE_ALLTOALLV;
     side_t snd, rcv;
     int rc = OMPI_SUCCESS;
-    if (ssig && (rc = side_init(m, &snd, 0, d->s.buf, d->s.dt, d->s.n, d->s.counts, d->s.count, d->s.disps, 0))) return rc;
+    if (ssig && (rc = side_init(m, &snd, 0, d->s.buf, d->s.dt, d->s.n, d->s.counts, d->s.count, d->s.disps, d->inplace ? 0 : 2)))
+        return rc;
     if (rsig && (rc = side_init(m, &rcv, 1, d->r.buf, d->r.dt, d->r.n, d->r.counts, d->r.count, d->r.disps, !d->inplace)))
         return rc;
     if (d->kind == MOVE_ALLTOALL && ssig && snd.bytes[0] != rcv.bytes[0]) return OMPI_ERR_BAD_PARAM;
-    int erc = ssig ? side_move(m, &snd, -1, 1) : d->inplace ? side_move(m, &rcv, every ? -1 : me, 1) : MI355X_SUCCESS;
+    int erc = ssig ? (snd.direct ? MI355X_SUCCESS : side_move(m, &snd, -1, 1)) : d->inplace ? side_move(m, &rcv, every ? -1 : me, 1) : MI355X_SUCCESS;
     if (erc != MI355X_SUCCESS) return map_rc(erc);
     mi355x_comm_t *e = m->engine;
     const void *sv = ssig ? snd.view : NULL;
     void *rv = rsig ? rcv.view : NULL;
     const size_t *sbytes = ssig ? snd.bytes : NULL, *soff = ssig ? snd.off : NULL;
     const size_t *rbytes = rsig ? rcv.bytes : NULL, *roff = rsig ? rcv.off : NULL;
+    if (ssig && snd.direct) {
+        /* the receive side: its layout when it is direct too, else its view (bytes), unpacked afterwards */
+        const int rdir = rsig && rcv.direct;
+        mi355x_ddt_t *rd = rdir ? rcv.d : NULL;
+        char *rb = !rsig ? NULL : rdir ? rcv.base : rcv.view;
+        const size_t *rc_ = !rsig ? NULL : rdir ? rcv.cnt : rcv.bytes, *rdis = !rsig ? NULL : rdir ? (const size_t *)rcv.udisp : rcv.off;
+        const size_t *sdis = (const size_t *)snd.udisp;  /* (not negative: side_init) */
+        switch (d->kind) {
+        case MOVE_GATHER: case MOVE_GATHERV:
+            erc = mi355x_gatherv_ddt2(e, snd.base + snd.udisp[0], snd.d, snd.cnt[0], rb, rd, rc_, rdis, root, NULL);
+            break;
+        case MOVE_SCATTER: case MOVE_SCATTERV:
+            erc = mi355x_scatterv_ddt2(e, snd.base, snd.d, snd.cnt, sdis, rb ? rb + (rdir ? rcv.udisp[0] : (ptrdiff_t)rcv.off[0]) : NULL,
+                                       rd, rsig ? rc_[0] : 0, root, NULL);
+            break;
+        case MOVE_ALLGATHERV:
+            erc = mi355x_allgatherv_ddt2(e, snd.base + snd.udisp[0], snd.d, snd.cnt[0], rb, rd, rc_, rdis, NULL);
+            break;
+        default: erc = mi355x_alltoallv_ddt2(e, snd.base, snd.d, snd.cnt, sdis, rb, rd, rc_, rdis, NULL); break;
+        }
+        if (erc == MI355X_SUCCESS && rsig && !rdir && (rcv.d || rcv.host)) {
+            erc = side_move(m, &rcv, -1, 0);
+            if (erc == MI355X_SUCCESS) erc = mi355x_stream_sync(NULL);
+        }
+        return map_rc(erc);
+    }
     if (rsig && rcv.direct) {
         const size_t *rdis = (const size_t *)rcv.udisp;  /* (not negative: side_init) */
         const size_t sb0 = ssig ? sbytes[0] : 0;
@@ -2108,6 +2142,7 @@ static int apply_engine_params(mca_coll_mi355x_module_t *m, struct ompi_communic
     KNOB(SELFTEST, mca_coll_mi355x_selftest != 0, "selftest");
     KNOB(NB_ORDER, mca_coll_mi355x_nb_order != 0, "nb_order");
     KNOB(SCAN_PART_MIN_BYTES, mca_coll_mi355x_scan_part_min, "scan_part_min_bytes");
+    KNOB(MOVE_SEND_MIN_RUN, mca_coll_mi355x_move_send_min_run, "move_send_min_run");
     KNOB(PIPE, mca_coll_mi355x_pipe_min_ranks > 0 && n >= mca_coll_mi355x_pipe_min_ranks, "pipe_min_ranks");
     KNOB(PIPE_CHUNK_KIB, mca_coll_mi355x_pipe_chunk_kib, "pipe_chunk_kib");
     KNOB(PIPE_WG_PER_CU, mca_coll_mi355x_pipe_wg_per_cu, "pipe_wg_per_cu");
@@ -2257,6 +2292,10 @@ static int component_register(void)
                  "forms take the engine's partitioned flow (each rank evaluates one block of every rank's prefix, "
                  "then the blocks are pulled) instead of the chain; 0 = never; the results do not depend on it",
                  OPAL_INFO_LVL_6, &mca_coll_mi355x_scan_part_min);
+    register_ull("move_send_min_run", "Shortest run, in bytes, of a derived send datatype on device memory that "
+                 "MPI_Gather(v) / MPI_Scatter(v) / MPI_Allgatherv / MPI_Alltoall(v) let the peers pull from directly "
+                 "(one run per block, not in place) instead of packing it first; 0 = never; the results do not depend "
+                 "on it and the ranks need not agree", OPAL_INFO_LVL_6, &mca_coll_mi355x_move_send_min_run);
     register_int("timeout_s", "Bound of every wait of the engine, seconds (0 = the engine's own: MI355X_TIMEOUT_S, "
                  "else one day -- MPI's waits are unbounded; a rank whose process is gone is noticed without it)",
                  OPAL_INFO_LVL_9, &mca_coll_mi355x_timeout_s);

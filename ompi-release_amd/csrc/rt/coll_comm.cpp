@@ -185,6 +185,7 @@ int mi355x_comm_create(const char *key, int rank, int size, int device, mi355x_c
     c->one_phase_max = (size_t)std::max(0.0, env_double("MI355X_ONE_PHASE_MAX_BYTES", (double)c->one_phase_max));
     c->nb_order = env_double("MI355X_NB_ORDER", 0.0) != 0.0 ? 1 : 0;
     c->scan_part_min = (size_t)std::max(0.0, env_double("MI355X_SCAN_PART_MIN_BYTES", (double)kScanPartMinDefault));
+    c->move_send_min_run = (size_t)std::max(0.0, env_double("MI355X_MOVE_SEND_MIN_RUN", (double)kMoveSendMinRunDefault));
     c->lat_on = env_double("MI355X_LAT_PROFILE", 0.0) != 0.0;
     c->rcache_max_maps = (size_t)std::max(0.0, env_double("MI355X_RCACHE_MAX_MAPS", 0.0));
     c->rcache_limit = (size_t)std::max(0.0, env_double("MI355X_RCACHE_SIZE_LIMIT", 0.0));
@@ -220,6 +221,7 @@ int mi355x_comm_create_loopback(int size, int device, mi355x_comm_t **comms)
         c->timeout_s = env_double("MI355X_TIMEOUT_S", kDefaultTimeoutS);
         c->nb_order = env_double("MI355X_NB_ORDER", 0.0) != 0.0 ? 1 : 0;
         c->scan_part_min = (size_t)std::max(0.0, env_double("MI355X_SCAN_PART_MIN_BYTES", (double)kScanPartMinDefault));
+        c->move_send_min_run = (size_t)std::max(0.0, env_double("MI355X_MOVE_SEND_MIN_RUN", (double)kMoveSendMinRunDefault));
         shared->refs++;
         comms[r] = c;
     }
@@ -253,6 +255,8 @@ int mi355x_comm_destroy(mi355x_comm_t *c)
     if (c->pipe_queue) (void)hipFree(c->pipe_queue);
     if (c->pipe_dbg) (void)hipHostFree(c->pipe_dbg);
     if (c->scratch) (void)hipFree(c->scratch);
+    if (c->rows2_dev) (void)hipFree(c->rows2_dev);
+    if (c->rows2_host) (void)hipHostFree(c->rows2_host);
     if (c->gf_buf) {  // (stream-ordered allocation, coll_gfold.cpp)
         (void)hipFreeAsync(c->gf_buf, nullptr);
         (void)hipStreamSynchronize(nullptr);
@@ -484,6 +488,8 @@ int mi355x_comm_get(const mi355x_comm_t *c, int knob, long *value)
     case MI355X_KNOB_NB_ORDER: *value = c->nb_order; break;
     case MI355X_KNOB_SCAN_PART_MIN_BYTES: *value = (long)c->scan_part_min; break;
     case MI355X_KNOB_MOVE_FUSED: *value = (long)c->move_fused; break;
+    case MI355X_KNOB_MOVE_SEND_DIRECT: *value = (long)c->move_send_direct; break;
+    case MI355X_KNOB_MOVE_SEND_MIN_RUN: *value = (long)c->move_send_min_run; break;
     default: return set_error(MI355X_ERR_ARG, "unknown knob %d", knob);
     }
     return MI355X_SUCCESS;
@@ -622,6 +628,11 @@ int mi355x_comm_set(mi355x_comm_t *c, int knob, long value)
         c->scan_part_min = (size_t)value;
         break;
     }
+    case MI355X_KNOB_MOVE_SEND_MIN_RUN:
+        // (the sender's choice alone: receivers serve either record, so the ranks need not agree)
+        if (value < 0) return set_error(MI355X_ERR_ARG, "move_send_min_run out of range");
+        c->move_send_min_run = (size_t)value;
+        break;
     case MI355X_KNOB_STAGE_BYTES:
         if (value < 4096 || value >= (1l << 31)) return set_error(MI355X_ERR_ARG, "stage_bytes out of range");
         if (c->stage) (void)hipFree(c->stage);

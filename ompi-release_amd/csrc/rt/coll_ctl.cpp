@@ -382,6 +382,27 @@ int local_handle(mi355x_comm *c, const void *p, BufDesc *d, bool force)
 
 namespace mi355x {
 
+// A rank that publishes a send LAYOUT lets its peers read wherever the layout reaches from the
+// published pointer.  What a peer gets mapped is the allocation that contains the pointer
+// (local_handle exports the allocation's base, the offset travels beside it), so every byte the
+// layout reaches must lie in that one allocation.
+int check_in_allocation(mi355x_comm *c, const void *p, size_t bytes, const char *what)
+{
+    (void)c;
+    if (bytes == 0) return MI355X_SUCCESS;
+    void *base = nullptr;
+    size_t sz = 0;
+    if (!p || hipMemGetAddressRange(&base, &sz, const_cast<void *>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_error(MI355X_ERR_ARG, "%s: %p is not device memory", what, p);
+    }
+    const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)p;
+    if (at < lo || bytes > sz - (size_t)(at - lo))
+        return set_error(MI355X_ERR_ARG, "%s: the layout reaches %zu bytes from %p, past its allocation (%zu bytes at %p)", what,
+                         bytes, p, sz, base);
+    return MI355X_SUCCESS;
+}
+
 // Publish nbuf local buffers, meet every rank, and resolve every rank's buffers:
 // peers[b][r] = rank r's buffer b mapped into this process.  When any rank published a buffer
 // that cannot be exported, nothing is mapped and *staged is set on every rank alike (callers

@@ -80,6 +80,151 @@ static void add_seg(MultiCopyArgs &m, const void *src, void *dst, size_t len)
     m.nseg++;
 }
 
+// The send side of a _ddt2 form as the impls take it: byte counts and displacements, and -- when
+// the layout is eligible (move_send_direct_ok) -- the rows this rank publishes instead of packing.
+// A NULL layout, or counts that are not significant here, is the _ddt form's send side (bytes); a
+// layout without gaps becomes bytes as RecvSide's does; any other layout that fails the rule sets rc
+// (MI355X_ERR_UNSUPPORTED: the caller packs), before the rank meets anybody.
+struct SendSide {
+    const RowLay *lay = nullptr;  // the published rows (NULL: dense bytes)
+    const size_t *counts, *displs;
+    int64_t first = 0;            // a gap-free layout's first byte (in displs already)
+    int rc = MI355X_SUCCESS;
+    RowLay rows{};
+    std::vector<size_t> bytes;
+    SendSide(mi355x_comm *c, const char *call, const void *sbuf, const mi355x_ddt *sddt, int n, const size_t *cnt,
+             const size_t *dsp)
+        : counts(cnt), displs(dsp)
+    {
+        if (!sddt || !cnt) return;
+        const SendShape sh = ddt_send_shape(sddt);
+        size_t most = 0;
+        for (int q = 0; q < n; ++q) most = std::max(most, cnt[q]);
+        const bool gap_free = send_gap_free(sh, most);
+        if (!gap_free && !move_send_direct_ok(sh, cnt, nullptr, n, sbuf == nullptr, (int64_t)c->move_send_min_run)) {
+            rc = set_error(MI355X_ERR_UNSUPPORTED, "%s: the send layout is not pulled from directly (%d runs per block, run %lld B, "
+                           "MOVE_SEND_MIN_RUN %zu%s): pack it", call, sh.nruns, (long long)sh.lay.run, c->move_send_min_run,
+                           sbuf ? "" : ", MPI_IN_PLACE");
+            return;
+        }
+        bytes.resize(2 * (size_t)n);
+        size_t reach = 0;
+        for (int q = 0; q < n; ++q) {
+            const size_t at = dsp ? dsp[q] : 0;
+            bytes[(size_t)q] = cnt[q] * (size_t)sh.size;
+            bytes[(size_t)(n + q)] = at + (gap_free ? (size_t)sh.lay.disp : 0);
+            if (cnt[q])
+                reach = std::max(reach, at + (size_t)((int64_t)(cnt[q] - 1) * sh.lay.extent + (sh.lay.nblk - 1) * sh.lay.stride +
+                                                      sh.lay.disp + sh.lay.run));
+        }
+        counts = bytes.data();
+        if (dsp) displs = bytes.data() + n;
+        if (gap_free) {
+            first = sh.lay.disp;
+            return;
+        }
+        rc = check_in_allocation(c, sbuf, reach, call);
+        rows = sh.lay;
+        lay = &rows;
+    }
+};
+
+// what this rank's published buffer holds for its peers: dense bytes, or the rows of `lay`
+static void publish_layout(mi355x_comm *c, const RowLay *lay)
+{
+    c->ctrl->slot[c->rank].slay = lay ? *lay : row_dense();
+}
+
+// The pieces of one rank's pull: k_multicopy's segments, and beside each the layout its owner
+// published for it.
+struct Pull {
+    MultiCopyArgs m;
+    RowLay sl[kMaxSegs];
+    bool rows = false;  // some piece is read through a send layout
+    Pull() { std::memset(&m, 0, sizeof(m)); }
+};
+
+static int add_piece(Pull &p, const void *src, const RankSlot &owner, void *dst, size_t len)
+{
+    const RowLay &l = owner.slay;
+    if (len == 0 || (l.nblk == 0 && src == dst)) return MI355X_SUCCESS;
+    if (l.nblk < 0 || (l.nblk && (l.run <= 0 || l.disp < 0 || l.nblk >= ((int64_t)1 << 32) || l.run >= ((int64_t)1 << 32))))
+        return set_error(MI355X_ERR_PEER, "a peer published a send layout this rank cannot read");
+    p.m.src[p.m.nseg] = src;
+    p.m.dst[p.m.nseg] = dst;
+    p.m.len[p.m.nseg] = len;
+    p.sl[p.m.nseg] = l;
+    p.rows = p.rows || l.nblk != 0;
+    p.m.nseg++;
+    return MI355X_SUCCESS;
+}
+
+static int rows2_table(mi355x_comm *c, Rows2Table *t)
+{
+    if (!c->rows2_dev) MI_HIP(hipMalloc(&c->rows2_dev, kRows2TableBytes));
+    if (!c->rows2_host) MI_HIP(hipHostMalloc(&c->rows2_host, kRows2TableBytes, hipHostMallocDefault));
+    t->dev = c->rows2_dev;
+    t->host = c->rows2_host;
+    return MI355X_SUCCESS;
+}
+
+// The pull, whatever the owners published.  No send layout among the pieces: copy_segments, the
+// kernels of the plain and _ddt forms.  Otherwise one launch of the two-ended row gather
+// (ddt_gather_segments) for all pieces, dense ones included, into rddt or dense bytes.  When that
+// declines -- rddt has several runs per block, or an end is beyond the 32-bit slot arithmetic -- the
+// dense pieces take copy_segments' kernels and the row pieces a launch of their own; and when rddt
+// is what it cannot take, the row pieces are gathered into the scratch as dense bytes (a dense
+// destination always applies to what move_send_direct_ok let a sender publish) and unpacked from
+// there (ddt_unpack_segments, as a _ddt form unpacks a peer's dense bytes).
+static int pull_segments(mi355x_comm *c, Pull &p, hipStream_t s, const mi355x_ddt *rddt)
+{
+    if (!p.rows) return copy_segments(c, p.m, s, rddt);
+    if (rddt) c->move_fused++;
+    Rows2Table tab;
+    int rc = rows2_table(c, &tab);
+    if (rc) return rc;
+    const int n = p.m.nseg;
+    Row2Seg all[kMaxSegs];
+    for (int i = 0; i < n; ++i) all[i] = Row2Seg{p.m.src[i], p.sl[i], p.m.dst[i], p.m.len[i]};
+    rc = ddt_gather_segments(rddt, all, n, tab, s);
+    if (rc != 1) return rc;
+    MultiCopyArgs dn;
+    std::memset(&dn, 0, sizeof(dn));
+    Row2Seg rw[kMaxSegs];
+    int nr = 0;
+    for (int i = 0; i < n; ++i) {
+        if (p.sl[i].nblk) rw[nr++] = all[i];
+        else add_seg(dn, p.m.src[i], p.m.dst[i], p.m.len[i]);
+    }
+    if (dn.nseg) {
+        rc = rddt ? ddt_unpack_segments(rddt, dn.src, dn.dst, dn.len, dn.nseg, s) : launch_multicopy(dn, s);
+        if (rc) return rc;
+    }
+    rc = ddt_gather_segments(rddt, rw, nr, tab, s);
+    if (rc != 1) return rc;
+    if (!rddt) return set_error(MI355X_ERR_UNSUPPORTED, "a published send layout is beyond the row gather's limits");
+    // two passes.  (The scratch is free: only alltoallv in place publishes it, and in place takes no rddt)
+    size_t total = 0;
+    const void *dsrc[kMaxSegs];
+    void *dmem[kMaxSegs];
+    size_t dlen[kMaxSegs];
+    for (int i = 0; i < nr; ++i) total += (rw[i].len + 15) & ~(size_t)15;
+    rc = ensure_scratch(c, total);
+    if (rc) return rc;
+    total = 0;
+    for (int i = 0; i < nr; ++i) {
+        dmem[i] = rw[i].mem;
+        dlen[i] = rw[i].len;
+        rw[i].mem = (char *)c->scratch + total;
+        dsrc[i] = rw[i].mem;
+        total += (rw[i].len + 15) & ~(size_t)15;
+    }
+    rc = ddt_gather_segments(nullptr, rw, nr, tab, s);
+    if (rc == 1) rc = set_error(MI355X_ERR_UNSUPPORTED, "a published send layout is beyond the row gather's limits");
+    if (rc) return rc;
+    return ddt_unpack_segments(rddt, dsrc, dmem, dlen, nr, s);
+}
+
 static int check_comm(mi355x_comm *c, int root)
 {
     if (!c) return set_error(MI355X_ERR_ARG, "comm is NULL");
@@ -93,8 +238,11 @@ static int check_comm(mi355x_comm *c, int root)
 // rddt (every impl below): NULL, or the receive layout -- rcounts are then instances of it, displs
 // still bytes, and the pull unpacks (copy_segments); everything up to the launch is the plain form's,
 // so a rank may call this form while its peers call the plain one.
+// slay (every impl below): NULL, or the rows this rank's send counts are read through -- the counts
+// stay bytes of the packed stream; the rank publishes sbuf itself and the record beside the counts.
 static int gatherv_impl(mi355x_comm *c, const void *sbuf, size_t sbytes, void *rbuf, const size_t *rcounts,
-                        const size_t *displs, int root, void *stream, const mi355x_ddt *rddt = nullptr)
+                        const size_t *displs, int root, void *stream, const mi355x_ddt *rddt = nullptr,
+                        const RowLay *slay = nullptr)
 {
     int rc = check_comm(c, root);
     if (rc) return rc;
@@ -107,23 +255,24 @@ static int gatherv_impl(mi355x_comm *c, const void *sbuf, size_t sbytes, void *r
     CallStream call_stream(c, s);
     MI_HIP(hipStreamSynchronize(s));
     c->ctrl->slot[c->rank].varg[0] = (int64_t)(sbuf ? sbytes : 0);
+    publish_layout(c, slay);
     const void *mine[1] = {sbytes ? sbuf : nullptr};
     const uint64_t sig[4] = {20, (uint64_t)root, 0, 0};
     std::vector<std::vector<void *>> P;
     rc = exchange(c, 1, mine, sig, P);
     if (rc) return rc;
     c->last_alg = 1;
+    if (slay && mine[0]) c->move_send_direct++;
     if (am_root) {
-        MultiCopyArgs m;
-        std::memset(&m, 0, sizeof(m));
+        Pull m;
         for (int q = 0; q < c->size; ++q) {
             const size_t qb = (size_t)c->ctrl->slot[q].varg[0];
             if (qb > piece_bytes(rddt, rcounts[q]))
                 return set_error(MI355X_ERR_TRUNCATE, "gatherv: rank %d sends %zu bytes, root expects %zu", q, qb,
                                  piece_bytes(rddt, rcounts[q]));
-            if (qb) add_seg(m, P[0][q], (char *)rbuf + displs[q], qb);
+            if (qb && (rc = add_piece(m, P[0][q], c->ctrl->slot[q], (char *)rbuf + displs[q], qb))) return rc;
         }
-        rc = copy_segments(c, m, s, rddt);
+        rc = pull_segments(c, m, s, rddt);
         if (rc) return rc;
     }
     return finish(c, s);
@@ -132,7 +281,8 @@ static int gatherv_impl(mi355x_comm *c, const void *sbuf, size_t sbytes, void *r
 // MPI_Scatterv: rank r pulls scounts[r] bytes at root's sbuf + displs[r] (both published by the
 // root) into rbuf (at most rbytes).  rbuf NULL at the root = MPI_IN_PLACE.
 static int scatterv_impl(mi355x_comm *c, const void *sbuf, const size_t *scounts, const size_t *displs, void *rbuf,
-                         size_t rbytes, int root, void *stream, const mi355x_ddt *rddt = nullptr)
+                         size_t rbytes, int root, void *stream, const mi355x_ddt *rddt = nullptr,
+                         const RowLay *slay = nullptr)
 {
     int rc = check_comm(c, root);
     if (rc) return rc;
@@ -149,22 +299,25 @@ static int scatterv_impl(mi355x_comm *c, const void *sbuf, const size_t *scounts
             c->ctrl->slot[c->rank].varg[kMaxRanks + q] = (int64_t)displs[q];
             any = any || scounts[q];
         }
+    if (!am_root) slay = nullptr;  // (no send side)
+    publish_layout(c, slay);
     const void *mine[1] = {am_root && any ? sbuf : nullptr};
     const uint64_t sig[4] = {21, (uint64_t)root, 0, 0};
     std::vector<std::vector<void *>> P;
     rc = exchange(c, 1, mine, sig, P);
     if (rc) return rc;
     c->last_alg = 1;
+    if (slay && mine[0]) c->move_send_direct++;
     const RankSlot &rs = c->ctrl->slot[root];
     const size_t len = (size_t)rs.varg[c->rank];
     if (rbuf && len) {
         if (len > piece_bytes(rddt, rbytes))
             return set_error(MI355X_ERR_TRUNCATE, "scatterv: root sends %zu bytes to rank %d, which expects %zu", len,
                              c->rank, piece_bytes(rddt, rbytes));
-        MultiCopyArgs m;
-        std::memset(&m, 0, sizeof(m));
-        add_seg(m, (const char *)P[0][root] + rs.varg[kMaxRanks + c->rank], rbuf, len);
-        rc = copy_segments(c, m, s, rddt);
+        Pull m;
+        rc = add_piece(m, (const char *)P[0][root] + rs.varg[kMaxRanks + c->rank], rs, rbuf, len);
+        if (rc) return rc;
+        rc = pull_segments(c, m, s, rddt);
         if (rc) return rc;
     }
     return finish(c, s);
@@ -173,7 +326,8 @@ static int scatterv_impl(mi355x_comm *c, const void *sbuf, const size_t *scounts
 // MPI_Allgatherv: every rank pulls rank q's block (rcounts[q] bytes) into rbuf + displs[q].
 // sbuf NULL = MPI_IN_PLACE (the rank's block is at rbuf + displs[rank]).
 static int allgatherv_impl(mi355x_comm *c, const void *sbuf, size_t sbytes, void *rbuf, const size_t *rcounts,
-                           const size_t *displs, void *stream, const mi355x_ddt *rddt = nullptr)
+                           const size_t *displs, void *stream, const mi355x_ddt *rddt = nullptr,
+                           const RowLay *slay = nullptr)
 {
     int rc = check_comm(c, 0);
     if (rc) return rc;
@@ -188,18 +342,21 @@ static int allgatherv_impl(mi355x_comm *c, const void *sbuf, size_t sbytes, void
     if (mybytes > piece_bytes(rddt, rcounts[me]))
         return set_error(MI355X_ERR_TRUNCATE, "allgatherv: rank %d sends %zu bytes, %zu expected", me, mybytes,
                          piece_bytes(rddt, rcounts[me]));
+    publish_layout(c, slay);
     const void *mine[1] = {mybytes ? src : nullptr};
     const uint64_t sig[4] = {22, 0, 0, 0};
     std::vector<std::vector<void *>> P;
     rc = exchange(c, 1, mine, sig, P);
     if (rc) return rc;
     c->last_alg = 1;
-    MultiCopyArgs m;
-    std::memset(&m, 0, sizeof(m));
+    if (slay && mine[0]) c->move_send_direct++;
+    Pull m;
     for (int q = 0; q < c->size; ++q)
-        if (rcounts[q] && P[0][q])
-            add_seg(m, P[0][q], (char *)rbuf + displs[q], q == me ? mybytes : piece_bytes(rddt, rcounts[q]));
-    rc = copy_segments(c, m, s, rddt);
+        if (rcounts[q] && P[0][q]) {
+            rc = add_piece(m, P[0][q], c->ctrl->slot[q], (char *)rbuf + displs[q], q == me ? mybytes : piece_bytes(rddt, rcounts[q]));
+            if (rc) return rc;
+        }
+    rc = pull_segments(c, m, s, rddt);
     if (rc) return rc;
     return finish(c, s);
 }
@@ -208,7 +365,8 @@ static int allgatherv_impl(mi355x_comm *c, const void *sbuf, size_t sbytes, void
 // (published by q) into rbuf + rdispls[q] (at most rcounts[q]).  sbuf NULL = MPI_IN_PLACE: the
 // data to send is rbuf laid out by rcounts / rdispls, snapshotted into scratch first.
 static int alltoallv_impl(mi355x_comm *c, const void *sbuf, const size_t *scounts, const size_t *sdispls, void *rbuf,
-                          const size_t *rcounts, const size_t *rdispls, void *stream, const mi355x_ddt *rddt = nullptr)
+                          const size_t *rcounts, const size_t *rdispls, void *stream, const mi355x_ddt *rddt = nullptr,
+                          const RowLay *slay = nullptr)
 {
     int rc = check_comm(c, 0);
     if (rc) return rc;
@@ -238,14 +396,15 @@ static int alltoallv_impl(mi355x_comm *c, const void *sbuf, const size_t *scount
         c->ctrl->slot[me].varg[kMaxRanks + q] = (int64_t)sdispls[q];
         any = any || scounts[q];
     }
+    publish_layout(c, slay);
     const void *mine[1] = {any ? src : nullptr};
     const uint64_t sig[4] = {23, 0, 0, 0};
     std::vector<std::vector<void *>> P;
     rc = exchange(c, 1, mine, sig, P);
     if (rc) return rc;
     c->last_alg = 1;
-    MultiCopyArgs m;
-    std::memset(&m, 0, sizeof(m));
+    if (slay && mine[0]) c->move_send_direct++;
+    Pull m;
     for (int k = 0; k < n; ++k) {
         const int q = (me + k) % n;   // own block first, then the peers in ring order
         const RankSlot &qs = c->ctrl->slot[q];
@@ -253,9 +412,10 @@ static int alltoallv_impl(mi355x_comm *c, const void *sbuf, const size_t *scount
         if (len > piece_bytes(rddt, rcounts[q]))
             return set_error(MI355X_ERR_TRUNCATE, "alltoallv: rank %d sends %zu bytes to rank %d, which expects %zu",
                              q, len, me, piece_bytes(rddt, rcounts[q]));
-        if (len) add_seg(m, (const char *)P[0][q] + qs.varg[kMaxRanks + me], (char *)rbuf + rdispls[q], len);
+        if (len && (rc = add_piece(m, (const char *)P[0][q] + qs.varg[kMaxRanks + me], qs, (char *)rbuf + rdispls[q], len)))
+            return rc;
     }
-    rc = copy_segments(c, m, s, rddt);
+    rc = pull_segments(c, m, s, rddt);
     if (rc) return rc;
     return finish(c, s);
 }
@@ -514,6 +674,76 @@ int mi355x_alltoallv_ddt(mi355x_comm_t *c, const void *sbuf, const size_t *scoun
     drain(c);
     CallGate gate(c);
     return alltoallv_impl(c, sbuf, scounts, sdispls, rbuf, r.counts, r.displs, stream, r.d);
+}
+
+// The _ddt2 forms: the _ddt forms with a send layout (SendSide).
+int mi355x_gatherv_ddt2(mi355x_comm_t *c, const void *sbuf, const mi355x_ddt_t *sddt, size_t scount, void *rbuf,
+                        const mi355x_ddt_t *rddt, const size_t *rcounts, const size_t *rdispls, int root, void *stream)
+{
+    if (!c) return set_error(MI355X_ERR_ARG, "comm is NULL");
+    DeviceGuard dg(c->device);
+    const SendSide sn(c, "gatherv", sbuf, sddt, 1, &scount, nullptr);
+    if (sn.rc) return sn.rc;
+    const RecvSide r(rddt, c->size, c->rank == root ? rcounts : nullptr, rdispls);
+    drain(c);
+    CallGate gate(c);
+    return gatherv_impl(c, sbuf ? (const char *)sbuf + sn.first : sbuf, sn.counts[0], rbuf, r.counts, r.displs, root, stream, r.d,
+                        sn.lay);
+}
+
+int mi355x_scatterv_ddt2(mi355x_comm_t *c, const void *sbuf, const mi355x_ddt_t *sddt, const size_t *scounts,
+                         const size_t *sdispls, void *rbuf, const mi355x_ddt_t *rddt, size_t rcount, int root, void *stream)
+{
+    if (!c) return set_error(MI355X_ERR_ARG, "comm is NULL");
+    DeviceGuard dg(c->device);
+    const bool am_root = c->rank == root;
+    if (am_root && sddt && (!scounts || !sdispls)) return set_error(MI355X_ERR_ARG, "scatterv: counts at the root are NULL");
+    // (in place at the root is rbuf NULL: the send side is significant and read by the others as usual)
+    const SendSide sn(c, "scatterv", sbuf, am_root ? sddt : nullptr, c->size, scounts, sdispls);
+    if (sn.rc) return sn.rc;
+    const RecvSide r(rddt, 1, &rcount, nullptr);
+    drain(c);
+    CallGate gate(c);
+    return scatterv_impl(c, sbuf, sn.counts, sn.displs, rbuf ? (char *)rbuf + r.first : rbuf, r.counts[0], root, stream, r.d,
+                         sn.lay);
+}
+
+int mi355x_allgatherv_ddt2(mi355x_comm_t *c, const void *sbuf, const mi355x_ddt_t *sddt, size_t scount, void *rbuf,
+                           const mi355x_ddt_t *rddt, const size_t *rcounts, const size_t *rdispls, void *stream)
+{
+    if (!c) return set_error(MI355X_ERR_ARG, "comm is NULL");
+    DeviceGuard dg(c->device);
+    const SendSide sn(c, "allgatherv", sbuf, sddt, 1, &scount, nullptr);
+    if (sn.rc) return sn.rc;
+    const RecvSide r(rddt, c->size, rcounts, rdispls);
+    drain(c);
+    CallGate gate(c);
+    return allgatherv_impl(c, sbuf ? (const char *)sbuf + sn.first : sbuf, sn.counts[0], rbuf, r.counts, r.displs, stream, r.d,
+                           sn.lay);
+}
+
+int mi355x_alltoallv_ddt2(mi355x_comm_t *c, const void *sbuf, const mi355x_ddt_t *sddt, const size_t *scounts,
+                          const size_t *sdispls, void *rbuf, const mi355x_ddt_t *rddt, const size_t *rcounts,
+                          const size_t *rdispls, void *stream)
+{
+    if (!c) return set_error(MI355X_ERR_ARG, "comm is NULL");
+    DeviceGuard dg(c->device);
+    if (sddt && sbuf && (!scounts || !sdispls)) return set_error(MI355X_ERR_ARG, "alltoallv: counts are NULL");
+    // (in place the send arguments are not read: only a layout with gaps is refused, as rddt's is)
+    if (sddt && !sbuf && !send_gap_free(ddt_send_shape(sddt), 2))
+        return set_error(MI355X_ERR_UNSUPPORTED, "alltoallv: MPI_IN_PLACE with a send layout");
+    const SendSide sn(c, "alltoallv", sbuf, sbuf ? sddt : nullptr, c->size, scounts, sdispls);
+    if (sn.rc) return sn.rc;
+    const RecvSide r(rddt, c->size, rcounts, rdispls);
+    drain(c);
+    CallGate gate(c);
+    return alltoallv_impl(c, sbuf, sn.counts, sn.displs, rbuf, r.counts, r.displs, stream, r.d, sn.lay);
+}
+
+int mi355x_move_send_direct_ok(const mi355x_comm_t *c, const mi355x_ddt_t *sddt, const size_t *scounts, int n)
+{
+    if (!c || !sddt || n < 0 || (n && !scounts)) return set_error(MI355X_ERR_ARG, "bad send layout arguments");
+    return move_send_direct_ok(ddt_send_shape(sddt), scounts, nullptr, n, false, (int64_t)c->move_send_min_run) ? 1 : 0;
 }
 
 int mi355x_alltoall(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, void *stream)

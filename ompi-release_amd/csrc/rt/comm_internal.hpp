@@ -20,6 +20,7 @@
 
 #include "coll_internal.hpp"
 #include "coll_sched.hpp"
+#include "ddt_rows_plan.hpp"
 #include "rt_internal.hpp"
 #include "svc_queue.hpp"
 
@@ -49,6 +50,8 @@ constexpr int kMaxBufs = 3;
 constexpr double kDefaultTimeoutS = 86400.0;
 // default of MI355X_KNOB_SCAN_PART_MIN_BYTES; measured, see BASELINE.md ("Partitioned scan")
 constexpr size_t kScanPartMinDefault = 0;
+// default of MI355X_KNOB_MOVE_SEND_MIN_RUN; measured, see BASELINE.md ("Pulling out of a send layout")
+constexpr size_t kMoveSendMinRunDefault = 16;
 constexpr int kVoteRing = 64;   // buffer-kind votes a rank keeps (mi355x_comm_vote)
 constexpr int kVoteWindow = 32;  // calls per vote window: every rank waits at each window's last call
 
@@ -78,6 +81,10 @@ struct alignas(64) RankSlot {
     int32_t probe_fd, probe_ok;   // dmabuf capability probe
     uint64_t probe_size;
     int64_t varg[2 * kMaxRanks];  // per-peer counts / displacements of v-collectives (bytes)
+    // the layout varg's counts are read through at this rank's published buffer (coll_move.cpp):
+    // dense bytes (nblk 0), or the rows of a send layout the rank did not pack; the counts stay
+    // bytes of the packed stream and the displacements bytes either way
+    RowLay slay;
     int32_t ll_ok, pad_ll;        // LL self-test result at creation (1 ok, 2 failed)
     int32_t svc_claim, svc_ok;    // resident LL service at creation: this process's service is mine
                                   // (1) or taken (2); its self-test passed (1) or failed (2)
@@ -416,6 +423,11 @@ struct mi355x_comm {
     uint64_t pipe_refused = 0;                    // calls that fell back because a token was taken
     uint64_t pipe_calls = 0;                      // allreduces served by the pipelined flow
     uint64_t move_fused = 0;                      // movement calls whose pull unpacked into a receive layout
+    uint64_t move_send_direct = 0;                // movement calls in which this rank published a send layout, packing nothing
+    // MI355X_KNOB_MOVE_SEND_MIN_RUN (env MI355X_MOVE_SEND_MIN_RUN): the shortest run, in bytes, of a send
+    // layout this rank publishes instead of packing; 0 = never.  The sender's choice alone
+    size_t move_send_min_run = mi355x::kMoveSendMinRunDefault;
+    void *rows2_dev = nullptr, *rows2_host = nullptr;  // the row gather's piece table (ddt_internal.hpp: Rows2Table)
     // finish() by device-written completion words (see RankSlot::done): the control segment
     // registered with HIP (hipHostRegister) and its device address; 0 = stream sync + barrier
     // MI355X_LAT_PROFILE=1: host time of the small-message allreduce's steps (entry -> input sync
@@ -476,6 +488,9 @@ int exchange(mi355x_comm *c, int nbuf, const void *const *mine, const uint64_t s
              bool persistent = false);
 int finish(mi355x_comm *c, hipStream_t s);          // stream sync + barrier
 int ensure_scratch(mi355x_comm *c, size_t bytes);   // exportable per-communicator scratch
+// [p, p + bytes) lies inside the one allocation that contains p -- the range a peer gets mapped
+// when p is published (coll_ctl.cpp)
+int check_in_allocation(mi355x_comm *c, const void *p, size_t bytes, const char *what);
 int run_program(int op, int type, const Program &pr, const std::vector<void *> &in,
                 const std::vector<void *> &dst, size_t off, size_t len, hipStream_t s);
 int check_common(mi355x_comm *c, int op, int type);

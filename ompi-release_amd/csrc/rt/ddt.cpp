@@ -303,6 +303,42 @@ int ddt_unpack_segments(const mi355x_ddt *d, const void *const *src, void *const
     }
     return MI355X_SUCCESS;
 }
+
+// The layout as rows, when it is rows: one run per block; or one block whose runs all have one
+// length and one spacing -- what a column is compiled to from opal's optimized description (one
+// ELEM record of strided elements, unrolled into runs), the same bytes in the same packed order as
+// nruns blocks of one run.  Only the two-ended gather reads a layout this way: pack, unpack and the
+// _ddt forms keep the kernels their run tables select.
+static bool row_view(const mi355x_ddt *d, RowLay *l)
+{
+    const size_t n = d->disp.size();
+    *l = RowLay{d->nblk, d->disp[0], d->len[0], d->stride, d->extent};
+    if (n == 1) return d->len[0] > 0;
+    if (d->nblk != 1 || d->len[0] <= 0) return false;
+    const int64_t step = d->disp[1] - d->disp[0];
+    for (size_t r = 1; r < n; ++r)
+        if (d->len[r] != d->len[0] || d->disp[r] - d->disp[r - 1] != step) return false;
+    *l = RowLay{(int64_t)n, d->disp[0], d->len[0], step, d->extent};
+    return true;
+}
+
+SendShape ddt_send_shape(const mi355x_ddt *d)
+{
+    SendShape sh;
+    sh.nruns = row_view(d, &sh.lay) ? 1 : (int)d->disp.size();
+    sh.size = d->nblk * blk_bytes(d);
+    return sh;
+}
+
+int ddt_gather_segments(const mi355x_ddt *d, const Row2Seg *segs, int nseg, const Rows2Table &tab, hipStream_t s)
+{
+    if (nseg < 0 || nseg > kRowsMaxSegs) return set_error(MI355X_ERR_ARG, "bad gather segments");
+    if (nseg == 0) return MI355X_SUCCESS;
+    if (!d) return launch_ddt_rows2_multi(row_dense(), segs, nseg, tab, s);
+    RowLay dst;
+    if (!row_view(d, &dst)) return 1;
+    return launch_ddt_rows2_multi(dst, segs, nseg, tab, s);
+}
 } // namespace mi355x
 
 extern "C" {

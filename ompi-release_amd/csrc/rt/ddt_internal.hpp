@@ -61,4 +61,22 @@ int launch_ddt_rows_multi(const DdtDev &d, int64_t run_disp, int64_t run_len, co
 int ddt_unpack_segments(const mi355x_ddt *d, const void *const *src, void *const *mem, const size_t *len, int nseg,
                         hipStream_t s);
 
+// the eligibility rule's view of a layout (ddt_rows_plan.hpp: move_send_direct_ok)
+SendShape ddt_send_shape(const mi355x_ddt *d);
+// the two-ended row gather's per-piece table: device memory the kernel reads, and the pinned host
+// copy it is filled in (both kRows2TableBytes; the communicator owns them, coll_move.cpp)
+constexpr size_t kRows2TableBytes = 64 * (size_t)kRowsMaxSegs;
+struct Rows2Table {
+    void *dev, *host;
+};
+// one launch: piece i read through its own source layout, written through dst (ddt_kernels.hip);
+// returns 1 when the plan declines (plan_rows2_multi: an end beyond the 32-bit slot arithmetic)
+int launch_ddt_rows2_multi(const RowLay &dst, const Row2Seg *segs, int nseg, const Rows2Table &tab, hipStream_t s);
+// the pull of a movement collective out of published send layouts: piece i = segs[i].len bytes read
+// through segs[i].s at segs[i].src, written through d laid at segs[i].mem (d NULL: dense bytes).  One
+// launch; returns 1 when it does not apply -- d has several runs per block, or the plan declines --
+// and the caller gathers into dense scratch first.  mi355x_ddt_tune_rows is not consulted: a receiver
+// serves whatever a sender was allowed to publish.  Nothing is waited for.
+int ddt_gather_segments(const mi355x_ddt *d, const Row2Seg *segs, int nseg, const Rows2Table &tab, hipStream_t s);
+
 } // namespace mi355x

@@ -164,21 +164,7 @@ __global__ __launch_bounds__(256) void k_ddt(DdtDev d, char *mem, char *packed, 
 // lanes of a wave on consecutive slots (one wave-instruction = 64 W contiguous packed bytes), all
 // U loads issued before the stores.  The two divisions per slot are 32-bit multiply-high
 // (Granlund-Montgomery magic numbers computed on the host), no 64-bit division, no search.
-struct FastDiv {
-    uint32_t m, l, d;
-};
-
-static FastDiv make_fastdiv(uint32_t d)
-{
-    FastDiv f;
-    f.d = d;
-    uint32_t l = 0;
-    while (l < 32 && ((uint64_t)1 << l) < d) ++l;
-    f.l = l;
-    f.m = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - d)) / d + 1);
-    return f;
-}
-
+// (FastDiv and make_fastdiv: ddt_rows_plan.hpp)
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv &f)
 {
     return (uint32_t)(((uint64_t)__umulhi(f.m, n) + n) >> f.l);
@@ -527,6 +513,140 @@ int launch_ddt_rows_multi(const DdtDev &d, int64_t run_disp, int64_t run_len, co
     // the load flavour and the non-temporal rule of k_multicopy, whose place this launch takes
     if (beyond_mall(2 * p.total)) launch_rows_multi_w<3>(p.w, unroll, m, tpb, p.first_block[p.nseg], s);
     else launch_rows_multi_w<0>(p.w, unroll, m, tpb, p.first_block[p.nseg], s);
+    MI_HIP(hipGetLastError());
+    return MI355X_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Two-ended row gather: the pull of a movement collective whose senders published their send
+// LAYOUTS instead of packing.  Piece i is len[i] bytes of a packed stream that exists nowhere: slot q
+// of it is read at the address the piece's SOURCE layout gives it (rows_pass' two divisions, on the
+// owner's record) and written at the address the receiver's one DESTINATION layout gives it (the
+// same two divisions) -- read once where the sender's application left it, written once where the
+// receiver's wants it.  Only the source may be remote, and it is only read; stores are local
+// (k_ddt_rows_multi's rule).  A dense end is the degenerate layout, one row: the destination's
+// divisions are templated away (DROWS), a dense piece among row pieces takes the pass without the
+// source divisions by a branch that is uniform per block.
+// The slot mapping (row_slot_off) lives in ddt_rows_plan.hpp, where the host check runs it against
+// a byte-by-byte enumeration of both layouts.
+// The per-piece table (two pointers, the source's strides and magic numbers: 64 B a piece, 4 KiB
+// for 64 pieces) does not fit HIP's kernel arguments beside first_block[]; it lies in device memory
+// (copied on the call's stream from the communicator's pinned staging copy) and a block reads the
+// ONE entry of its piece, with wave-uniform loads, after finding the piece in first_block[] (by
+// value, as k_ddt_rows_multi).  Staging all entries in LDS would read 64 entries to use one.
+struct alignas(16) Rows2Piece {
+    const char *src;  // the piece's base + the source run's displacement
+    char *dst;        // ... the destination's
+    RowEnd s;
+    uint32_t nslots;
+    uint32_t s_rows;  // 0: the source is dense
+};
+static_assert(sizeof(Rows2Piece) * kRowsMaxSegs == kRows2TableBytes, "the communicator's table holds one launch");
+struct Rows2Args {
+    const Rows2Piece *tab;
+    RowEnd d;
+    int nseg;
+    unsigned first_block[kRowsMaxSegs + 1];
+};
+
+template <int NTM, int U, int W, bool SROWS, bool DROWS>
+__device__ __forceinline__ void rows2_pass(const Rows2Piece &p, const RowEnd &d, uint32_t base, uint32_t tpb)
+{
+    typedef typename SlotT<W>::type S;
+    S v[U];
+    char *dp[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const uint32_t i = base + (uint32_t)u * tpb;
+        dp[u] = nullptr;
+        if (i < p.nslots) {
+            const S *src = reinterpret_cast<const S *>(p.src + row_slot_off<W, SROWS>(p.s, i));
+            dp[u] = p.dst + row_slot_off<W, DROWS>(d, i);
+            if constexpr ((NTM & 1) != 0) v[u] = __builtin_nontemporal_load(src);
+            else v[u] = *src;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (dp[u]) {
+            S *dst = reinterpret_cast<S *>(dp[u]);
+            if constexpr ((NTM & 2) != 0) __builtin_nontemporal_store(v[u], dst);
+            else *dst = v[u];
+        }
+    }
+}
+
+template <int NTM, int U, int W, bool DROWS>
+__global__ __launch_bounds__(256) void k_ddt_rows2_multi(Rows2Args m)
+{
+    int sgi = 0;
+    while (sgi + 1 < m.nseg && blockIdx.x >= m.first_block[sgi + 1]) ++sgi;
+    const unsigned nb = m.first_block[sgi + 1] - m.first_block[sgi];
+    const unsigned b = blockIdx.x - m.first_block[sgi];
+    const Rows2Piece p = m.tab[sgi];  // (uniform per block)
+    const uint32_t tpb = blockDim.x;
+    const uint64_t per = (uint64_t)tpb * U;
+    if (p.s_rows) {
+        for (uint64_t base = (uint64_t)b * per + threadIdx.x; base < p.nslots; base += (uint64_t)nb * per)
+            rows2_pass<NTM, U, W, true, DROWS>(p, m.d, (uint32_t)base, tpb);
+    } else {
+        for (uint64_t base = (uint64_t)b * per + threadIdx.x; base < p.nslots; base += (uint64_t)nb * per)
+            rows2_pass<NTM, U, W, false, DROWS>(p, m.d, (uint32_t)base, tpb);
+    }
+}
+
+constexpr unsigned kRows2Threads = 256;
+constexpr int kRows2Unroll16 = 4;  // slots per lane at W = 16 (kNarrowUnroll below it)
+
+template <int NTM, bool DROWS>
+static void launch_rows2_w(int w, const Rows2Args &m, unsigned blocks, hipStream_t s)
+{
+    const dim3 g(blocks), t(kRows2Threads);
+    switch (w) {
+    case 16: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kRows2Unroll16, 16, DROWS>), g, t, 0, s, m); break;
+    case 8: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kNarrowUnroll, 8, DROWS>), g, t, 0, s, m); break;
+    case 4: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kNarrowUnroll, 4, DROWS>), g, t, 0, s, m); break;
+    case 2: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kNarrowUnroll, 2, DROWS>), g, t, 0, s, m); break;
+    default: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kNarrowUnroll, 1, DROWS>), g, t, 0, s, m); break;
+    }
+}
+
+int launch_ddt_rows2_multi(const RowLay &dst, const Row2Seg *segs, int nseg, const Rows2Table &tab, hipStream_t s)
+{
+    if (!tab.dev || !tab.host) return set_error(MI355X_ERR_ARG, "row gather without a piece table");
+    const size_t cap = (size_t)coll_tune().blocks_per_cu * (size_t)device_cu_count();
+    const RowsMultiPlan p = plan_rows2_multi(dst, segs, nseg, kRows2Threads * (unsigned)kRows2Unroll16,
+                                             kRows2Threads * (unsigned)kNarrowUnroll, cap);
+    if (p.w == 0) return 1;
+    if (p.nseg == 0) return MI355X_SUCCESS;
+    Rows2Piece *host = static_cast<Rows2Piece *>(tab.host);
+    for (int i = 0; i < p.nseg; ++i) {
+        const Row2Seg &g = segs[p.seg[i]];
+        Rows2Piece &e = host[i];
+        e.src = static_cast<const char *>(g.src) + (g.s.nblk ? g.s.disp : 0);
+        e.dst = static_cast<char *>(g.mem) + (dst.nblk ? dst.disp : 0);
+        e.s = row_end(g.s, p.w);
+        e.nslots = (uint32_t)(g.len / (size_t)p.w);
+        e.s_rows = g.s.nblk ? 1u : 0u;
+    }
+    // the pinned copy is free again when the call that filled it returns (every movement call ends
+    // at finish(): its stream has passed this copy and the kernel behind it)
+    MI_HIP(hipMemcpyAsync(tab.dev, tab.host, sizeof(Rows2Piece) * (size_t)p.nseg, hipMemcpyHostToDevice, s));
+    Rows2Args m;
+    std::memset(&m, 0, sizeof(m));
+    m.tab = static_cast<const Rows2Piece *>(tab.dev);
+    m.d = row_end(dst, p.w);
+    m.nseg = p.nseg;
+    for (int i = 0; i <= p.nseg; ++i) m.first_block[i] = p.first_block[i];
+    const unsigned blocks = p.first_block[p.nseg];
+    // the load flavour and the non-temporal rule of launch_ddt_rows_multi
+    if (dst.nblk) {
+        if (beyond_mall(2 * p.total)) launch_rows2_w<3, true>(p.w, m, blocks, s);
+        else launch_rows2_w<0, true>(p.w, m, blocks, s);
+    } else {
+        if (beyond_mall(2 * p.total)) launch_rows2_w<3, false>(p.w, m, blocks, s);
+        else launch_rows2_w<0, false>(p.w, m, blocks, s);
+    }
     MI_HIP(hipGetLastError());
     return MI355X_SUCCESS;
 }

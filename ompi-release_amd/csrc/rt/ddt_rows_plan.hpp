@@ -3,13 +3,46 @@
 //   * rows_width: the slot width one window of a row layout (one run per block) can move with;
 //   * plan_rows_multi: one launch unpacking several packed pieces into the same row layout (the pull
 //     of a movement collective into a derived receive datatype): which pieces it keeps, the slot
-//     width they share and the blocks each one gets.
+//     width they share and the blocks each one gets;
+//   * move_send_direct_ok: which send layouts a movement collective publishes instead of packing;
+//   * plan_rows2_multi: the same plan for the two-ended row gather (k_ddt_rows2_multi), whose pieces
+//     are read through a row layout of their own and written through the receiver's.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
 
+// the few functions a kernel shares with the host checks (the divisions and the slot mapping)
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define MI355X_HD __host__ __device__ inline
+#else
+#define MI355X_HD inline
+#endif
+
 namespace mi355x {
+
+// 32-bit division by a constant as a multiply-high and a shift (Granlund-Montgomery; the magic
+// numbers are computed on the host once per launch): exact for every 32-bit n and d >= 1
+struct FastDiv {
+    uint32_t m, l, d;
+};
+
+inline FastDiv make_fastdiv(uint32_t d)
+{
+    FastDiv f;
+    f.d = d;
+    uint32_t l = 0;
+    while (l < 32 && ((uint64_t)1 << l) < d) ++l;
+    f.l = l;
+    f.m = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - d)) / d + 1);
+    return f;
+}
+
+MI355X_HD uint32_t fast_div(uint32_t n, const FastDiv &f)
+{
+    return (uint32_t)(((((uint64_t)f.m * n) >> 32) + n) >> f.l);
+}
 
 // largest slot index the 32-bit row / unit kernels take: their grid-stride and last-block index
 // arithmetic (at most 2^22 slots past the end) must not wrap
@@ -52,6 +85,23 @@ struct RowsMultiPlan {
     size_t total;                            // bytes of the kept pieces
 };
 
+// the blocks of a plan's kept pieces (segs[p.seg[s]].len bytes each, p.total in all) at slot width w
+template <class Seg>
+inline void deal_row_blocks(RowsMultiPlan &p, const Seg *segs, int w, size_t per, size_t cap)
+{
+    unsigned next = 0;
+    for (int s = 0; s < p.nseg; ++s) {
+        p.first_block[s] = next;
+        const size_t len = segs[p.seg[s]].len, nslots = len / (size_t)w;
+        const size_t want = (nslots + per - 1) / per;
+        const size_t share = (cap * len + p.total - 1) / p.total;
+        size_t nb = want < share ? want : share;
+        if (nb == 0) nb = 1;
+        next += (unsigned)nb;
+    }
+    p.first_block[p.nseg] = next;
+}
+
 // Skips the pieces that hold no bytes and those whose packed source is their own memory base
 // (nothing to move: k_multicopy's src == dst rule).  W is the widest power of two <= 16 that
 // rows_width allows for EVERY kept piece -- its packed address, its memory address, its length,
@@ -78,18 +128,150 @@ inline RowsMultiPlan plan_rows_multi(int64_t stride, int64_t extent, int64_t nbl
         p.seg[p.nseg++] = i;
         p.total += segs[i].len;
     }
-    const size_t per = w == 16 ? per16 : per_narrow;
-    unsigned next = 0;
-    for (int s = 0; s < p.nseg; ++s) {
-        p.first_block[s] = next;
-        const size_t len = segs[p.seg[s]].len, nslots = len / (size_t)w;
-        const size_t want = (nslots + per - 1) / per;
-        const size_t share = (cap * len + p.total - 1) / p.total;
-        size_t nb = want < share ? want : share;
-        if (nb == 0) nb = 1;
-        next += (unsigned)nb;
+    deal_row_blocks(p, segs, w, w == 16 ? per16 : per_narrow, cap);
+    p.w = w;
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------------
+// One end of the two-ended row gather: a row layout (one run of `run` bytes per block at `disp`,
+// nblk blocks `stride` apart, instances `extent` apart), or dense bytes (nblk == 0: the piece is one
+// row of its own length).  Also the record a sender publishes next to its counts (RankSlot::slay).
+struct RowLay {
+    int64_t nblk;  // 0: dense
+    int64_t disp, run, stride, extent;
+};
+inline RowLay row_dense() { return RowLay{0, 0, 0, 0, 0}; }
+
+// A send layout as the eligibility rule reads it (ddt.cpp fills it from a mi355x_ddt).
+struct SendShape {
+    int nruns;       // runs per block
+    RowLay lay;      // the first run's row layout (meaningful when nruns == 1)
+    int64_t size;    // packed bytes of one instance
+};
+
+// `most` instances leave no gap: the plain call (ddt_contiguous's rule)
+inline bool send_gap_free(const SendShape &sh, size_t most)
+{
+    if (sh.nruns != 1) return false;
+    if (sh.lay.nblk > 1 && sh.lay.stride != sh.lay.run) return false;
+    return most <= 1 || sh.lay.extent == sh.lay.nblk * sh.lay.run;
+}
+
+// May a sender publish this layout for its peers to pull from, instead of packing it?  All of:
+// one run per block; not gap-free for the call's largest count (that is the plain call); not in
+// place; no byte below the buffer (run displacement, stride and extent >= 0 wherever they count);
+// every piece displacement >= 0 (displs may be NULL: none are given); every piece's packed size
+// below kSlot32Max bytes and run length and block count within 32 bits, so that a receiver can always
+// serve the piece at slot width 1; the run at least min_run bytes, and min_run not 0 (never).
+inline bool move_send_direct_ok(const SendShape &sh, const size_t *counts, const int64_t *displs, int n, bool in_place,
+                                int64_t min_run)
+{
+    if (sh.nruns != 1 || in_place || min_run <= 0 || n < 0 || (n && !counts)) return false;
+    const RowLay &l = sh.lay;
+    if (l.run <= 0 || l.run < min_run || l.nblk < 1 || l.disp < 0) return false;
+    size_t most = 0;
+    for (int q = 0; q < n; ++q) most = counts[q] > most ? counts[q] : most;
+    if (send_gap_free(sh, most)) return false;
+    if ((l.nblk > 1 && l.stride < 0) || (most > 1 && l.extent < 0)) return false;
+    if (l.run >= ((int64_t)1 << 32) || l.nblk >= ((int64_t)1 << 32) || sh.size != l.nblk * l.run) return false;
+    for (int q = 0; q < n; ++q) {
+        if (displs && displs[q] < 0) return false;
+        if (counts[q] >= (size_t)kSlot32Max / (size_t)sh.size + 1) return false;  // (no overflow in the product)
+        if ((int64_t)counts[q] * sh.size >= kSlot32Max) return false;
     }
-    p.first_block[p.nseg] = next;
+    return true;
+}
+
+// One end as the kernel holds it (the run's displacement is folded into the end's base pointer),
+// and the byte offset of W-byte slot q of a piece's packed stream from that base: rows_pass' two
+// divisions, or q * W for a dense end.
+struct RowEnd {
+    int64_t stride, extent;
+    FastDiv per_row, per_inst;  // slots per row, rows per instance
+};
+
+inline RowEnd row_end(const RowLay &l, int w)
+{
+    RowEnd e;
+    e.stride = l.nblk ? l.stride : 0;
+    e.extent = l.nblk ? l.extent : 0;
+    e.per_row = make_fastdiv(l.nblk ? (uint32_t)(l.run / w) : 1u);
+    e.per_inst = make_fastdiv(l.nblk ? (uint32_t)l.nblk : 1u);
+    return e;
+}
+
+template <int W, bool ROWS> MI355X_HD int64_t row_slot_off(const RowEnd &e, uint32_t q)
+{
+    if constexpr (!ROWS) return (int64_t)q * W;
+    else {
+        const uint32_t g = fast_div(q, e.per_row);
+        const uint32_t w = q - g * e.per_row.d;
+        const uint32_t k = fast_div(g, e.per_inst);
+        const uint32_t j = g - k * e.per_inst.d;
+        return (int64_t)k * e.extent + (int64_t)j * e.stride + (int64_t)w * W;
+    }
+}
+
+// One launch of the two-ended gather.  Piece i: `len` bytes of a packed stream, read through the
+// source layout `s` laid at `src` (possibly a peer's memory), written through the launch's one
+// destination layout laid at `mem`; both from position 0 of the stream.
+struct Row2Seg {
+    const void *src;
+    RowLay s;
+    void *mem;
+    size_t len;
+};
+
+// the widest width (16 .. 1) one end of a piece allows, 0: the 32-bit slot arithmetic does not hold it
+inline int rows2_end_width(const RowLay &l, const void *base, size_t len)
+{
+    if (l.nblk == 0) {
+        const uint64_t bits = (uintptr_t)base | (uint64_t)len;
+        int w = 16;
+        while (w > 1 && (bits & (uint64_t)(w - 1))) w >>= 1;
+        return (int64_t)(len / (size_t)w) >= kSlot32Max ? 0 : w;
+    }
+    return rows_width(l.stride, l.extent, l.nblk, 1, l.disp, l.run, base, nullptr, 0, (int64_t)len);
+}
+
+// plan_rows_multi's contract with two ends.  Kept: the pieces that hold bytes (in the caller's
+// order); p.seg / p.nseg / p.total as there.  W is the widest power of two <= 16 that EVERY kept
+// piece allows on BOTH ends: for a row end its first byte (base + disp), run length, stride and
+// extent, for a dense end (one row) its base; and the piece length.  An end beyond the 32-bit slot
+// arithmetic (rows_width's limits; a dense end: kSlot32Max slots) makes the plan decline (w = 0).
+// Blocks are dealt exactly as plan_rows_multi deals them.
+inline RowsMultiPlan plan_rows2_multi(const RowLay &dst, const Row2Seg *segs, int nseg, unsigned per16, unsigned per_narrow,
+                                      size_t cap)
+{
+    RowsMultiPlan p;
+    p.w = 0;
+    p.nseg = 0;
+    p.total = 0;
+    p.first_block[0] = 0;
+    if (nseg > kRowsMaxSegs || per16 == 0 || per_narrow == 0) return p;
+    int w = 16;
+    for (int i = 0; i < nseg; ++i) {
+        if (segs[i].len == 0) continue;
+        const int ws = rows2_end_width(segs[i].s, segs[i].src, segs[i].len);
+        const int wd = rows2_end_width(dst, segs[i].mem, segs[i].len);
+        if (ws == 0 || wd == 0) return p;
+        if (ws < w) w = ws;
+        if (wd < w) w = wd;
+        p.seg[p.nseg++] = i;
+        p.total += segs[i].len;
+    }
+    // each end was checked at its own width; the shared W may be narrower, so the counts larger
+    for (int s = 0; s < p.nseg; ++s) {
+        const Row2Seg &g = segs[p.seg[s]];
+        const int64_t rs = g.s.nblk ? g.s.run / w : 0, rd = dst.nblk ? dst.run / w : 0;
+        if ((int64_t)(g.len / (size_t)w) >= kSlot32Max || rs >= ((int64_t)1 << 32) || rd >= ((int64_t)1 << 32)) {
+            p.nseg = 0;
+            p.total = 0;
+            return p;
+        }
+    }
+    deal_row_blocks(p, segs, w, w == 16 ? per16 : per_narrow, cap);
     p.w = w;
     return p;
 }
