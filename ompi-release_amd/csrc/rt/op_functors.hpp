@@ -30,11 +30,14 @@ struct cf32 { float re, im; };
 struct cf64 { double re, im; };
 // MAXLOC/MINLOC pairs, byte-identical to the C structs of op_base_functions.c:539-555 on
 // x86-64 (gfx950 uses the same sizes and alignments for these members).
+// The padding is a member: a selected pair carries its padding bytes with it, so every kernel that
+// evaluates one program stores the same bytes (an unnamed gap the compiler leaves unset: the 16-byte
+// vector paths of k_fold and k_pipe_allreduce stored different bytes there for the same call).
 struct p_float_int { float v; int k; };
-struct p_double_int { double v; int k; };
-struct p_long_int { long v; int k; };
+struct p_double_int { double v; int k; int pad; };
+struct p_long_int { long v; int k; int pad; };
 struct p_2int { int v; int k; };
-struct p_short_int { short v; int k; };
+struct p_short_int { short v; short pad; int k; };
 static_assert(sizeof(p_float_int) == 8, "float_int");
 static_assert(sizeof(p_double_int) == 16, "double_int");
 static_assert(sizeof(p_long_int) == 16, "long_int");
@@ -102,6 +105,7 @@ MI_DEV f80 operator*(const f80 &a, const f80 &b) { return f80_of(x87::mul(f80_bi
 struct alignas(16) p_ldouble_int {
     f80 v;
     int k;
+    int pad[3];
 };
 static_assert(sizeof(p_ldouble_int) == 32, "long_double_int");
 
@@ -238,6 +242,12 @@ template <> MI_DEV f80 copysgn<f80>(f80 m, f80 s)
     return m;
 }
 template <> MI_DEV f80 cst<f80>(double v) { return f80_of(x87::from_double(v)); }
+// A NaN component of a product leaves as the default quiet NaN.  Which operand's sign and payload a
+// multiply or add passes on depends on the order the compiler gives the instruction its operands,
+// so two kernels evaluating the same program (the pipelined and the two-phase allreduce) stored
+// different bits here; MPI defines none.  The x87 arithmetic is restated in integers and has one order.
+template <typename R> MI_DEV R canon_nan(R x) { return is_nan(x) ? (R)__builtin_nan("") : x; }
+template <> MI_DEV f80 canon_nan<f80>(f80 x) { return x; }
 
 // (a + ib) * (c + id) as GCC evaluates `_Complex` multiplication without -ffast-math:
 // x = ac - bd, y = ad + bc; if both are NaN, libgcc's __mul?c3 recovery rules (C99 G.5.1).
@@ -274,8 +284,8 @@ template <typename R> MI_DEV typename CplxOf<R>::type cmul(R a, R b, R c, R d)
         }
     }
     typename CplxOf<R>::type r;
-    r.re = x;
-    r.im = y;
+    r.re = canon_nan(x);
+    r.im = canon_nan(y);
     return r;
 }
 

@@ -1493,6 +1493,318 @@ def token_check(key, rank, size, dev):
     print(f"rank {rank} token_check OK", flush=True)
 
 
+class _Off:
+    """what the parts of the offalign mode share: guarded buffers (devbuf.Buf) for every operand, the
+    oracle's results computed once per input and reused across shifts, and the checks made after
+    every call -- result bits (opdata.assert_same), the result's guards, the input unchanged and
+    its guards -- collected per part, so one run shows the whole pattern of a failure"""
+
+    KNOBS = ("ALLREDUCE_ALG", "REDUCE_ALG", "REDUCE_SCATTER_ALG", "SVC_MAX_BYTES", "LL_MAX_BYTES", "SVC_PULL_MAX_BYTES",
+             "SVC_PULL_COPY_MAX_BYTES", "ONE_PHASE_MAX_BYTES", "PIPE", "PIPE_WT", "PIPE_CHUNK_KIB")
+
+    def __init__(self, pkg, comm, rank, size, oracle, torch):
+        import devbuf
+        import offalign_plan
+        self.pkg, self.comm, self.rank, self.size, self.oracle, self.torch = pkg, comm, rank, size, oracle, torch
+        self.Buf, self.knobs, self.plan = devbuf.Buf, devbuf.knobs, offalign_plan
+        self.cache = {}
+        self.bad = []
+
+    @staticmethod
+    def ptrs(arrs):
+        return (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+
+    def inputs(self, tname, count, salt=1100):
+        key = ("x", tname, count, salt)
+        if key not in self.cache:
+            self.cache[key] = [opdata.make(tname, count, salt + r) for r in range(self.size)]
+        return self.cache[key]
+
+    def want_allreduce(self, opname, tname, count, alg):
+        """(every rank's inputs, my expected result, the algorithm the reference runs)"""
+        key = ("ar", opname, tname, count, alg)
+        if key not in self.cache:
+            xs = self.inputs(tname, count)
+            outs = [np.zeros_like(xs[0]) for _ in range(self.size)]
+            ran = self.oracle.oracle_allreduce(alg, self.size, count, self.pkg.T[tname], self.pkg.OP[opname], 0,
+                                               self.ptrs(xs), self.ptrs(outs))
+            assert ran >= 0
+            self.cache[key] = (outs[self.rank], ran)
+        return (self.inputs(tname, count),) + self.cache[key]
+
+    def want_reduce(self, opname, tname, count, root):
+        key = ("red", opname, tname, count, root)
+        if key not in self.cache:
+            xs = self.inputs(tname, count)
+            want = np.zeros_like(xs[0])
+            assert self.oracle.oracle_reduce(0, self.size, root, count, self.pkg.T[tname], self.pkg.OP[opname], 0,
+                                             self.ptrs(xs), want.ctypes.data) >= 0
+            self.cache[key] = want
+        return self.inputs(tname, count), self.cache[key]
+
+    def expect(self, ok, msg):
+        if not ok:
+            self.bad.append(msg[:300])
+
+    def check(self, what, dr, dx, orig, same=None, raw=None):
+        """dr: the result buffer (None: this rank receives nothing); dx: the input buffer (dr itself in
+        place); same = (type, op, expected) for opdata.assert_same, raw = expected bytes"""
+        if dr is not None:
+            if same is not None:
+                try:
+                    opdata.assert_same(same[0], same[1], dr.get(), same[2], what)
+                except AssertionError as e:
+                    self.bad.append(str(e)[:300])
+            if raw is not None:
+                got = dr.raw()
+                diff = np.flatnonzero(got != raw)
+                self.expect(len(diff) == 0, f"{what}: {len(diff)} wrong bytes, the first at {diff[0] if len(diff) else -1}")
+            self.expect(dr.guards_intact(), f"{what}: wrote outside the result buffer")
+        if dx is not None and dx is not dr:
+            self.expect(dx.holds(orig), f"{what}: the input changed")
+            self.expect(dx.guards_intact(), f"{what}: wrote outside the input buffer")
+
+    def done(self, part):
+        bad, self.bad = self.bad, []
+        assert not bad, f"offalign part {part}: {len(bad)} failures\n" + "\n".join(bad[:8])
+
+    # ---- single calls
+    def allreduce(self, what, opname, tname, count, alg, s, r, inplace):
+        xs, want, ran = self.want_allreduce(opname, tname, count, alg)
+        x = xs[self.rank]
+        dr = self.Buf(self.torch, x, count, r, x if inplace else None)
+        dx = dr if inplace else self.Buf(self.torch, x, count, s, x)
+        self.torch.cuda.synchronize()
+        self.comm.allreduce(None if inplace else dx.ptr, dr.ptr, count, self.pkg.T[tname], self.pkg.OP[opname])
+        what = f"{what} allreduce {opname}/{tname} count={count} alg={alg} shifts=({s},{r}) inplace={inplace} rank={self.rank}"
+        self.check(what, dr, dx, x, same=(tname, opname, want))
+        self.expect(self.comm.last_algorithm() == ran, f"{what}: algorithm {self.comm.last_algorithm()}, the reference ran {ran}")
+        return dr
+
+    def reduce(self, what, opname, tname, count, root, s, r):
+        xs, want = self.want_reduce(opname, tname, count, root)
+        x = xs[self.rank]
+        dx = self.Buf(self.torch, x, count, s, x)
+        dr = self.Buf(self.torch, x, count, r) if self.rank == root else None
+        self.torch.cuda.synchronize()
+        self.comm.reduce(dx.ptr, dr.ptr if dr else None, count, self.pkg.T[tname], self.pkg.OP[opname], root)
+        self.check(f"{what} reduce {opname}/{tname} count={count} root={root} shifts=({s},{r}) rank={self.rank}", dr, dx, x,
+                   same=(tname, opname, want))
+
+    @staticmethod
+    def pattern(q, nb):
+        """rank q's bytes: they change along the block, and differ from every other rank's at every offset"""
+        return ((np.arange(nb, dtype=np.uint32) * 131 + 17 * q + nb) % 251).astype(np.uint8)
+
+    def allgather(self, what, nb, s, d, inplace, alg=None):
+        mine = self.pattern(self.rank, nb)
+        init = np.zeros(nb * self.size, dtype=np.uint8)
+        if inplace:
+            init[self.rank * nb:(self.rank + 1) * nb] = mine
+        dst = self.Buf(self.torch, init, nb * self.size, d, init)
+        src = None if inplace else self.Buf(self.torch, mine, nb, s, mine)
+        self.torch.cuda.synchronize()
+        self.comm.allgather(None if inplace else src.ptr, dst.ptr, nb)
+        what = f"{what} allgather {nb} bytes shifts=({s},{d}) inplace={inplace} rank={self.rank}"
+        self.check(what, dst, src, mine, raw=np.concatenate([self.pattern(q, nb) for q in range(self.size)]))
+        if alg is not None:
+            self.expect(self.comm.last_algorithm() == alg, f"{what}: algorithm {self.comm.last_algorithm()}, not {alg}")
+
+    def bcast(self, what, nb, s, d, root, alg=None):
+        mine = self.pattern(self.rank, nb)
+        shift = s if self.rank == root else d
+        b = self.Buf(self.torch, mine, nb, shift, mine)
+        self.torch.cuda.synchronize()
+        self.comm.bcast(b.ptr, nb, root)
+        what = f"{what} bcast {nb} bytes root={root} shift={shift} rank={self.rank}"
+        self.check(what, b, None, None, raw=self.pattern(root, nb))
+        if alg is not None:
+            self.expect(self.comm.last_algorithm() == alg, f"{what}: algorithm {self.comm.last_algorithm()}, not {alg}")
+
+    # ---- the tables
+    def ll_table(self, what, limit, algs, arrangements):
+        """parts (a) and (b): the allreduce / reduce table and the allgather / bcast table; returns
+        the calls made (reductions, copies)"""
+        plan, nred, ncopy = self.plan, 0, 0
+        for opname, tname, esz, align, pairs in plan.SLOTS:
+            for i, arr in plan.ll_cases(pairs, arrangements):
+                s, r = plan.shifts(pairs, i, arr, self.rank)
+                for nbytes in plan.payload_sizes(esz, limit):
+                    for alg in algs:
+                        self.comm.set("ALLREDUCE_ALG", alg)
+                        for inplace in (False, True):
+                            self.allreduce(f"{what} {arr}", opname, tname, nbytes // esz, alg, s, r, inplace)
+                            nred += 1
+                    for root in plan.roots(self.size):
+                        self.reduce(f"{what} {arr}", opname, tname, nbytes // esz, root, s, r)
+                        nred += 1
+        self.comm.set("ALLREDUCE_ALG", 0)
+        cus = self.torch.cuda.get_device_properties(0).multi_processor_count
+        for nb in plan.ll_copy_sizes(limit):
+            # LL (3) unless the ranks sharing a GPU could not all be resident at once (ll_checks' condition)
+            alg = 3 if ((nb + 4095) // 4096) * self.size <= cus else None
+            for s, d in plan.LL_COPY_SHIFTS:
+                for inplace in (False, True):
+                    self.allgather(what, nb, s, d, inplace, alg)
+                for root in plan.roots(self.size):
+                    self.bcast(what, nb, s, d, root)
+                ncopy += 2 + len(plan.roots(self.size))
+        return nred, ncopy
+
+
+def offalign(key, rank, size, dev):
+    """the cross-process flows on buffers off 16-byte alignment, with guards (tests/offalign_plan.py
+    holds the case tables; test_offalign_plan.py shows which branches they enter):
+      (a) the resident service's LL forms, (b) the per-call LL kernels, (c) the service's pull
+      allreduce, served and refused for alignment, (d) its pull copies and reduce_scatter form --
+      all up to 8 ranks -- and (e) the pipelined allreduce at every size.
+    Every buffer is a devbuf.Buf; expected bits are the oracle's schedule simulation; after every
+    call the result's guards, the unchanged input and the input's guards are checked.  Prints the
+    number of calls every part made, for the test to compare with the plan's own counts."""
+    import faulthandler
+    import json
+    faulthandler.dump_traceback_later(150, exit=True)  # a rank stuck in a HIP call names its line
+    import torch
+    torch.cuda.set_device(dev)
+    pkg = load_pkg()
+    oracle = load_oracle()
+    comm = pkg.Comm.create(key, rank, size, dev)
+    o = _Off(pkg, comm, rank, size, oracle, torch)
+    plan, knobs = o.plan, o.knobs
+    # the first small call runs the device setup and claims the service (its self-tests count as calls)
+    o.allreduce("warm-up", "SUM", "FLOAT", 1000, 0, 0, 0, False)
+    o.done("warm-up")
+    found = {k: comm.get(k) for k in o.KNOBS}
+    svc0 = comm.get("SVC_CALLS")
+    n = dict.fromkeys(("a_red", "a_copy", "b_red", "b_copy", "c_served", "c_refused", "c_back_to_back", "d_copy", "d_rs",
+                       "e_pipe", "e_two_phase"), 0)
+    n.update(svc_max=0, ll_max=0, pull_max=0)
+    if size <= plan.LL_MAX_RANKS:
+        assert comm.get("SVC_OWNER") == 1, "the only communicator of the job owns the resident service"
+        svc_max = n["svc_max"] = comm.get("SVC_MAX_BYTES")
+        assert svc_max > 0
+        # ---- (a) the service's LL forms: every call is one service call
+        calls0 = comm.get("SVC_CALLS")
+        n["a_red"], n["a_copy"] = o.ll_table("service", svc_max, plan.AR_ALGS, plan.ARRANGEMENTS)
+        served = comm.get("SVC_CALLS") - calls0
+        o.expect(served == n["a_red"] + n["a_copy"], f"(a) the service served {served} of {n['a_red'] + n['a_copy']} calls")
+        o.done("a")
+        # ---- (b) the per-call LL kernels
+        with knobs([comm], SVC_MAX_BYTES=0, LL_MAX_BYTES=256 << 10):
+            ll_max = n["ll_max"] = comm.get("LL_MAX_BYTES")
+            assert ll_max == 256 << 10, "the creation-time self-test disabled the LL path"
+            n["b_red"], n["b_copy"] = o.ll_table("LL", ll_max, (0,), ("rotated",))
+        o.done("b")
+        # ---- (c) the pull allreduce: served, refused for one rank's sbuf, for one rank's rbuf, served again
+        with knobs([comm], SVC_PULL_MAX_BYTES=1 << 20, ALLREDUCE_ALG=4):
+            assert comm.get("SVC_PULL_MAX_BYTES") == 1 << 20
+            for opname, tname in plan.PULL_SLOTS:
+                _, _, esz, align, _ = plan.slot(opname, tname)
+                for count in plan.pull_counts(svc_max, esz):
+                    steps = [("aligned", 0, 0, 1), ("sbuf of the last rank shifted", align if rank == size - 1 else 0, 0, 0),
+                             ("rbuf of rank 0 shifted", 0, align if rank == 0 else 0, 0), ("aligned again", 0, 0, 1)]
+                    for name, s, r, rise in steps:
+                        calls0 = comm.get("SVC_CALLS")
+                        o.allreduce(f"pull, {name}:", opname, tname, count, 4, s, r, False)
+                        got = comm.get("SVC_CALLS") - calls0
+                        o.expect(got == rise, f"pull, {name}: {opname}/{tname} count={count} rank={rank}: SVC_CALLS rose by "
+                                              f"{got}, expected {rise}")
+                        n["c_served" if rise else "c_refused"] += 1
+            # back to back after the refusals: the LL slots' parity and the service's doorbell still in step
+            calls0 = comm.get("SVC_CALLS")
+            for k in range(plan.PULL_BACK_TO_BACK):
+                x = np.full(1000, float(rank + k), dtype=np.float32)
+                dx, dr = o.Buf(torch, x, 1000, 0, x), o.Buf(torch, x, 1000)
+                torch.cuda.synchronize()
+                comm.allreduce(dx.ptr, dr.ptr, 1000, pkg.T["FLOAT"], pkg.OP["SUM"])
+                o.check(f"back to back after the refusals, call {k}, rank={rank}", dr, dx, x,
+                        raw=np.full(1000, float(sum(q + k for q in range(size))), dtype=np.float32).view(np.uint8))
+                n["c_back_to_back"] += 1
+            got = comm.get("SVC_CALLS") - calls0
+            o.expect(got == plan.PULL_BACK_TO_BACK, f"back to back after the refusals: the service served {got} calls")
+        o.done("c")
+        # ---- (d) the pull copies and the reduce_scatter form
+        calls0 = comm.get("SVC_CALLS")
+        for nb in plan.pull_copy_sizes(svc_max):
+            for s, d in plan.PULL_COPY_SHIFTS:
+                for inplace in (False, True):
+                    o.allgather("pull", nb, s, d, inplace, 1)
+                for root in plan.roots(size):
+                    o.bcast("pull", nb, s, d, root, 1)
+                n["d_copy"] += 2 + len(plan.roots(size))
+        got = comm.get("SVC_CALLS") - calls0
+        o.expect(got == n["d_copy"], f"(d) the service served {got} of {n['d_copy']} allgather / bcast calls")
+        limit = n["pull_max"] = comm.get("SVC_PULL_MAX_BYTES")
+        calls0, expect = comm.get("SVC_CALLS"), 0
+        for rsalg in plan.RS_ALGS:
+            comm.set("REDUCE_SCATTER_ALG", rsalg)
+            for opname, tname in plan.RS_SLOTS:
+                _, _, esz, align, pairs = plan.slot(opname, tname)
+                op, ty = pkg.OP[opname], pkg.T[tname]
+                for rcounts in plan.rs_counts(size, limit, esz):
+                    xs = o.inputs(tname, sum(rcounts), 1300 + 10 * rsalg)
+                    outs = [np.zeros(k, dtype=xs[0].dtype) for k in rcounts]
+                    assert oracle.oracle_reduce_scatter_alg(rsalg, size, (ctypes.c_int * size)(*rcounts), ty, op,
+                                                            o.ptrs(xs), o.ptrs(outs)) >= 0
+                    for s, r in pairs[:2]:
+                        dx = o.Buf(torch, xs[rank], sum(rcounts), s, xs[rank])
+                        dr = o.Buf(torch, xs[rank], rcounts[rank], r)
+                        torch.cuda.synchronize()
+                        comm.reduce_scatter(dx.ptr, dr.ptr, rcounts, ty, op)
+                        o.check(f"service reduce_scatter {opname}/{tname} alg={rsalg} rcounts={rcounts[:3]} shifts=({s},{r}) "
+                                f"rank={rank}", dr, dx, xs[rank], same=(tname, opname, outs[rank]))
+                        n["d_rs"] += 1
+                        expect += max(rcounts) * esz <= limit
+        comm.set("REDUCE_SCATTER_ALG", 0)
+        got = comm.get("SVC_CALLS") - calls0
+        o.expect(got == expect, f"(d) the service served {got} reduce_scatter calls, expected {expect}")
+        o.done("d")
+    # ---- (e) the pipelined allreduce, at every size
+    svc1, pipe0 = comm.get("SVC_CALLS"), comm.get("PIPE_CALLS")
+    differ = []   # pipelined results whose bytes are not the two-phase flow's
+    with knobs([comm], PIPE=1, SVC_MAX_BYTES=0, LL_MAX_BYTES=0, ONE_PHASE_MAX_BYTES=0, ALLREDUCE_ALG=4,
+               PIPE_CHUNK_KIB=plan.PIPE_CHUNK_KIB, PIPE_WT=1):
+        assert comm.get("PIPE") == 1, "the creation-time self-test disabled the pipelined flow"
+        for opname, tname, esz, align in plan.PIPE_SLOTS:
+            count, dt = plan.pipe_count(size, esz), opdata.dtype_of(tname)
+            for layout in plan.pipe_layouts(esz, align):
+                s, r = plan.pipe_shifts(layout, align, rank)
+                for inplace in (False, True):
+                    bits = []
+                    for pipe, wt in ((1, 0), (1, 1), (0, 1)):
+                        comm.set("PIPE", pipe)
+                        comm.set("PIPE_WT", wt)
+                        calls0, refused0 = comm.get("PIPE_CALLS"), comm.get("PIPE_REFUSED")
+                        dr = o.allreduce(f"pipe={pipe} wt={wt} {layout}:", opname, tname, count, 4, s, r, inplace)
+                        rose = (comm.get("PIPE_CALLS") - calls0, comm.get("PIPE_REFUSED") - refused0)
+                        o.expect(rose == (pipe, 0), f"pipe={pipe} wt={wt} {layout} {opname}/{tname} inplace={inplace} rank={rank}: "
+                                                    f"PIPE_CALLS, PIPE_REFUSED rose by {rose}")
+                        bits.append(dr.raw())   # device bytes: numpy's copy() of a pair leaves its padding unset
+                        n["e_pipe" if pipe else "e_two_phase"] += 1
+                    for b, name in zip(bits[:2], ("fenced", "write-through")):
+                        diff = np.flatnonzero(b != bits[2])
+                        if len(diff):
+                            differ.append(f"{layout} {opname}/{tname} inplace={inplace} rank={rank}: the {name} pipelined "
+                                          f"result differs from the two-phase flow's in {len(diff)} bytes of "
+                                          f"{len(set(diff // esz))} elements ({len(opdata.mismatches(tname, opname, b.view(dt), bits[2].view(dt)))} "
+                                          f"of them differ under opdata's rules), the "
+                                          f"first at byte {diff[0] % esz} of element {diff[0] // esz}")
+    o.done("e")
+    if size > plan.LL_MAX_RANKS:
+        assert comm.get("SVC_CALLS") == svc0 == svc1, "no service call past 8 ranks"
+    assert comm.get("PIPE_CALLS") - pipe0 == n["e_pipe"]
+    left = {k: comm.get(k) for k in o.KNOBS}
+    assert left == found, f"knobs not restored: {found} -> {left}"
+    print(f"rank {rank} offalign calls {json.dumps(n)}", flush=True)
+    comm.barrier()
+    comm.destroy()
+    # everything above held: the oracle's bits, the guards, the inputs, the counters, the knobs
+    kinds = sorted({" ".join(d.split(" ", 2)[:2]) for d in differ})   # (layout, slot) of every differing result
+    assert not differ, (f"offalign part e: {len(differ)} pipelined results are not the two-phase flow's bytes "
+                        f"({', '.join(kinds)})\n" + "\n".join(differ[:6]))
+    print(f"rank {rank} offalign OK", flush=True)
+
+
 def main():
     try:
         _main()
@@ -1537,6 +1849,8 @@ def _main():
         return svc_mode(key, rank, size, dev)
     if len(sys.argv) > 5 and sys.argv[5] == "svc_stress":
         return svc_stress(key, rank, size, dev)
+    if len(sys.argv) > 5 and sys.argv[5] == "offalign":
+        return offalign(key, rank, size, dev)
     import faulthandler
     faulthandler.dump_traceback_later(150, exit=True)  # a rank stuck in a HIP call names its line
     import torch
