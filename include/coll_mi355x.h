@@ -164,6 +164,7 @@ extern int mca_coll_mi355x_selftest;                     /* 1 */
 extern int mca_coll_mi355x_nb_order;                     /* 0: coll/tuned's order for the nonblocking reductions; 1: coll/libnbc's */
 extern unsigned long long mca_coll_mi355x_scan_part_min; /* bytes per rank from which scan / exscan take the partitioned flow; 0: never */
 extern unsigned long long mca_coll_mi355x_move_send_min_run; /* shortest run (bytes) of a derived send side the movement calls publish instead of packing (16); 0: never */
+extern int mca_coll_mi355x_move_row_levels; /* levels of rows the movement calls read a derived device layout as: 2 (default) a 3-D subarray is pulled like a vector, 1 it is a run list */
 /* the engine of a communicator coll/mi355x serves (NULL otherwise): for tools and tests */
 struct mi355x_comm *mca_coll_mi355x_engine_of(struct ompi_communicator_t *comm);
 

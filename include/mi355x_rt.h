@@ -277,7 +277,7 @@ enum mi355x_knob {
     MI355X_KNOB_MOVE_SEND_DIRECT = 47,   /* (read-only) movement calls in which this rank published a send layout
                                            (the _ddt2 forms below) and packed nothing: its peers read the rows
                                            where the application left them */
-    MI355X_KNOB_MOVE_SEND_MIN_RUN = 48   /* (per communicator; the ranks need not agree -- the choice is the
+    MI355X_KNOB_MOVE_SEND_MIN_RUN = 48,  /* (per communicator; the ranks need not agree -- the choice is the
                                            sender's alone and a receiver serves either record; env
                                            MI355X_MOVE_SEND_MIN_RUN at creation) the shortest run, in bytes, of a
                                            send layout this rank publishes directly instead of packing; 0 = never.
@@ -287,6 +287,24 @@ enum mi355x_knob {
                                            of pack + plain call at 2, 4 and 8 ranks ("Pulling out of
                                            a send layout").  What a strided read of short runs costs across xGMI
                                            that run cannot show: raise the knob there if it loses. */
+    MI355X_KNOB_MOVE_ROW_LEVELS = 49,    /* (per communicator; the ranks need not agree -- a receiver serves
+                                           whatever a sender was allowed to publish; env MI355X_MOVE_ROW_LEVELS at
+                                           creation, where another value is ignored; set takes 1 or 2, anything
+                                           else is MI355X_ERR_ARG) how many levels of rows
+                                           the movement calls read a layout as (mi355x_ddt_row_levels).  2: a
+                                           two-level send layout (the pencil of a 3-D array) is published like a
+                                           vector, and a two-level receive layout takes one launch for all peers.
+                                           1: only one run per block, or one block of equally spaced runs, is
+                                           rows -- anything else is a run list: packed by the caller on the send
+                                           side, unpacked peer by peer on the receive side.  The results do not
+                                           depend on it.  Default 2: with the ranks sharing ONE GPU an alltoall
+                                           of the z-pencils of a 3-D array of floats or doubles, 64 MiB per rank,
+                                           rows of 16, 64, 256 and 4096 bytes, took 0.31 .. 0.82 of pack + plain
+                                           / _ddt call at 2, 4 and 8 ranks, on the send side alone and on both
+                                           ("Pulling through 3-D subarray layouts").  No strided read
+                                           crossed xGMI in that run: lower the knob there if it loses. */
+    MI355X_KNOB_MOVE_PULL_LAUNCHES = 50  /* (read-only) kernels the pulls of this communicator's movement calls
+                                           have launched (one for all peers where a pull is one launch) */
 };
 /* cross-device flows (MI355X_KNOB_FLOWS) */
 enum mi355x_flow {
@@ -384,8 +402,9 @@ typedef struct mi355x_ddt mi355x_ddt_t;  /* a datatype layout of the GPU convert
  * instance or inside a run and leave the rest of the piece untouched.  The send side is as in the
  * plain forms (bytes), and every step before the pull is theirs, so in one collective some ranks
  * may call a _ddt form and the others the plain one.  A layout of one run per block (vector,
- * subarray rows, a resized column) takes one launch for all peers; a layout with several runs per
- * block one per peer.  rddt NULL (counts are then bytes) or a layout without gaps is the plain
+ * subarray rows, a resized column) takes one launch for all peers; so does, under
+ * MI355X_KNOB_MOVE_ROW_LEVELS = 2, any other layout that mi355x_ddt_row_levels reads as rows (a 3-D
+ * subarray, an hvector of vectors); a run list takes one launch per peer.  rddt NULL (counts are then bytes) or a layout without gaps is the plain
  * call.  MPI_IN_PLACE with a layout that has gaps (sbuf NULL in allgatherv / alltoallv, or at the
  * root of gatherv) returns MI355X_ERR_UNSUPPORTED before the rank meets its peers.  Calls that
  * pull this way are counted by MI355X_KNOB_MOVE_FUSED.  rddt is not read on a rank that receives
@@ -407,11 +426,13 @@ int mi355x_alltoallv_ddt(mi355x_comm_t *comm, const void *sbuf, const size_t *sc
  * so in one collective the _ddt2, _ddt and plain forms meet: a peer that sends dense bytes publishes
  * the "dense" record.  sddt NULL: the send counts are bytes and the call is exactly the _ddt form;
  * a layout without gaps is that call too.  Any other sddt must pass the rule of
- * mi355x_move_send_direct_ok -- one run per block; not MPI_IN_PLACE; no byte below sbuf; every
- * piece below 2^32 - 2^22 packed bytes; the run at least MI355X_KNOB_MOVE_SEND_MIN_RUN bytes, and
- * that knob not 0 -- else the call returns MI355X_ERR_UNSUPPORTED before the rank meets its peers
+ * mi355x_move_send_direct_ok -- rows (mi355x_ddt_row_levels not 0) of no more levels than
+ * MI355X_KNOB_MOVE_ROW_LEVELS admits; not MPI_IN_PLACE; no byte below sbuf; every piece below
+ * 2^32 - 2^22 packed bytes; the run at least MI355X_KNOB_MOVE_SEND_MIN_RUN bytes, and that knob
+ * not 0 -- else the call returns MI355X_ERR_UNSUPPORTED before the rank meets its peers
  * and the caller packs as before.  Every byte the layout reaches must lie in the allocation that
- * contains sbuf (MI355X_ERR_ARG otherwise).  A receive layout with several runs per block takes two
+ * contains sbuf (MI355X_ERR_ARG otherwise).  A receive layout that is a run list (or rows that this
+ * rank's MOVE_ROW_LEVELS does not read as rows) takes two
  * passes (the rows gathered into the communicator's scratch, then unpacked).  sddt is not read on a
  * rank that sends nothing significant (scatterv off the root).  Calls in which this rank published
  * a layout are counted by MI355X_KNOB_MOVE_SEND_DIRECT; MI355X_KNOB_MOVE_FUSED keeps counting the
@@ -427,7 +448,7 @@ int mi355x_alltoallv_ddt2(mi355x_comm_t *comm, const void *sbuf, const mi355x_dd
                           const size_t *sdispls, void *rbuf, const mi355x_ddt_t *rddt, const size_t *rcounts,
                           const size_t *rdispls, void *stream);
 /* the rule above for n pieces of scounts[] instances of sddt, not in place, under the communicator's
- * MOVE_SEND_MIN_RUN: 1 the layout would be published, 0 it would not (the caller packs; a layout
+ * MOVE_SEND_MIN_RUN and MOVE_ROW_LEVELS: 1 the layout would be published, 0 it would not (the caller packs; a layout
  * without gaps is the plain call), or a negative status.  Host only. */
 int mi355x_move_send_direct_ok(const mi355x_comm_t *comm, const mi355x_ddt_t *sddt, const size_t *scounts, int n);
 int mi355x_scan(mi355x_comm_t *comm, const void *sbuf, void *rbuf, size_t count, int type, int op, void *stream);
@@ -575,6 +596,13 @@ int mi355x_ddt_destroy(mi355x_ddt_t *d);
 size_t mi355x_ddt_size(const mi355x_ddt_t *d);
 int64_t mi355x_ddt_extent(const mi355x_ddt_t *d);
 int mi355x_ddt_nruns(const mi355x_ddt_t *d);
+/* how the movement collectives read the layout: 1 rows (runs of one length, rows one step apart,
+ * instances one extent apart: a vector, a column, a 2-D block), 2 rows in groups (one more count and
+ * step: the pencil or slab of a 3-D array, a 3-D subarray, an hvector of vectors -- whether compiled to
+ * several equal runs per block or to one block whose runs are a two-level progression), 0 a run list
+ * (anything else).  Levels of count 1 and levels that continue the one below them do not count.
+ * Host only; no knob changes the answer. */
+int mi355x_ddt_row_levels(const mi355x_ddt_t *d);
 /* launch shape of the single-run (row) pack/unpack kernel: 16-B slots per lane for pack and for
  * unpack (2/4/8; 0 keeps), threads per block (256/512/1024; 0 keeps), nontemporal -2 keep,
  * -1 auto (non-temporal above 256 MiB moved), 0..3 mask (1 = loads, 2 = stores) */

@@ -165,6 +165,7 @@ def _declare(lib: ctypes.CDLL) -> None:
         "mi355x_ddt_size": (sz, [vp]),
         "mi355x_ddt_extent": (c.c_int64, [vp]),
         "mi355x_ddt_nruns": (i, [vp]),
+        "mi355x_ddt_row_levels": (i, [vp]),
         "mi355x_ddt_tune": (i, [i, i, i, i]),
         "mi355x_ddt_tune_rows": (i, [i]),
         "mi355x_comm_vote": (i, [vp, i, c.POINTER(i)]),
@@ -292,7 +293,8 @@ KNOB = {"ALLREDUCE_ALG": 1, "REDUCE_ALG": 2, "REDUCE_SCATTER_ALG": 3, "BLOCKS_PE
         "SVC_OWNER": 33, "SVC_CLAIMS": 34, "SVC_IDLE_US": 35,
         "SVC_SHRINK_US": 36, "SVC_REGROWS": 37, "DEV_SETUP": 38, "SETUP_US": 39, "SELFTEST": 40,
         "PIPE_CALLS": 41, "EXPORT_MISMATCHES": 42, "SELFTEST_REUSED": 43, "NB_ORDER": 44,
-        "SCAN_PART_MIN_BYTES": 45, "MOVE_FUSED": 46, "MOVE_SEND_DIRECT": 47, "MOVE_SEND_MIN_RUN": 48}
+        "SCAN_PART_MIN_BYTES": 45, "MOVE_FUSED": 46, "MOVE_SEND_DIRECT": 47, "MOVE_SEND_MIN_RUN": 48,
+        "MOVE_ROW_LEVELS": 49, "MOVE_PULL_LAUNCHES": 50}
 # coll/libnbc's algorithms (mi355x_comm_last_algorithm under NB_ORDER = 1, mi355x_nbc_decision)
 NBC_ALG = {"BINOMIAL": 101, "RING": 102, "CHAIN": 103}
 FLOW = {"SVC_LL": 1, "SVC_PULL": 2, "SVC_COPY": 4, "SVC_RS": 8, "PIPE": 16}
@@ -675,6 +677,10 @@ class Ddt:
     @property
     def nruns(self):
         return int(rt().mi355x_ddt_nruns(self.h))
+
+    def row_levels(self):
+        """mi355x_ddt_row_levels: 0 a run list, 1 rows, 2 rows in groups, as the movement collectives read it"""
+        return int(rt().mi355x_ddt_row_levels(self.h))
 
     def pack(self, count, base, pos, dst, nbytes, stream=None, checksum=False):
         cs = ctypes.c_uint32()

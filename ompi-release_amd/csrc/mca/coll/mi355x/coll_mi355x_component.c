@@ -293,6 +293,7 @@ int mca_coll_mi355x_selftest = 1;
 int mca_coll_mi355x_nb_order = 0;
 unsigned long long mca_coll_mi355x_scan_part_min = 0;  /* measured: BASELINE.md, "Partitioned scan" */
 unsigned long long mca_coll_mi355x_move_send_min_run = 16;  /* measured: BASELINE.md, "Pulling out of a send layout" */
+int mca_coll_mi355x_move_row_levels = 2;  /* measured: BASELINE.md, "Pulling through 3-D subarray layouts" */
 int mca_coll_mi355x_timeout_s = 0;  /* 0: the engine's own (MI355X_TIMEOUT_S, else one day) */
 
 /* 1: the call runs in the engine (a rank with host buffers joins on device copies); 0: it runs in
@@ -1083,7 +1084,8 @@ static int movement_staged(mca_coll_mi355x_module_t *m, const movement_t *d, str
  * A derived receive side in device memory, not in place, has no scratch and no unpack of its own: the
  * engine's _ddt form pulls the peers' bytes straight into the layout (the fixed-count kinds through the
  * v-forms, with the per-piece arrays of side_init).  A derived send side in device memory, not in place,
- * that the engine's rule admits (one run per block, runs of coll_mi355x_move_send_min_run bytes or more)
+ * that the engine's rule admits (rows of one level, or of two under coll_mi355x_move_row_levels = 2 -- the
+ * pencil of a 3-D array -- with runs of coll_mi355x_move_send_min_run bytes or more)
  * has no scratch and no pack either: the _ddt2 form publishes the layout and the peers pull out of it.
  * Every rank still makes the same engine collective -- the _ddt2, the _ddt and the plain forms meet -- so
  * the path depends on no rank-local layout; only this rank's publication and the kernel of its own pull do. */
@@ -2143,6 +2145,7 @@ static int apply_engine_params(mca_coll_mi355x_module_t *m, struct ompi_communic
     KNOB(NB_ORDER, mca_coll_mi355x_nb_order != 0, "nb_order");
     KNOB(SCAN_PART_MIN_BYTES, mca_coll_mi355x_scan_part_min, "scan_part_min_bytes");
     KNOB(MOVE_SEND_MIN_RUN, mca_coll_mi355x_move_send_min_run, "move_send_min_run");
+    KNOB(MOVE_ROW_LEVELS, mca_coll_mi355x_move_row_levels, "move_row_levels");
     KNOB(PIPE, mca_coll_mi355x_pipe_min_ranks > 0 && n >= mca_coll_mi355x_pipe_min_ranks, "pipe_min_ranks");
     KNOB(PIPE_CHUNK_KIB, mca_coll_mi355x_pipe_chunk_kib, "pipe_chunk_kib");
     KNOB(PIPE_WG_PER_CU, mca_coll_mi355x_pipe_wg_per_cu, "pipe_wg_per_cu");
@@ -2296,6 +2299,11 @@ static int component_register(void)
                  "MPI_Gather(v) / MPI_Scatter(v) / MPI_Allgatherv / MPI_Alltoall(v) let the peers pull from directly "
                  "(one run per block, not in place) instead of packing it first; 0 = never; the results do not depend "
                  "on it and the ranks need not agree", OPAL_INFO_LVL_6, &mca_coll_mi355x_move_send_min_run);
+    register_int("move_row_levels", "Levels of rows the movement collectives read a derived datatype on device memory "
+                 "as: 2 = a 3-D subarray / hvector of vectors (rows in groups) is pulled from directly on the send side "
+                 "and takes one launch on the receive side, like a vector; 1 = only one run per block is rows, such a "
+                 "type is packed / unpacked peer by peer; the results do not depend on it and the ranks need not agree",
+                 OPAL_INFO_LVL_6, &mca_coll_mi355x_move_row_levels);
     register_int("timeout_s", "Bound of every wait of the engine, seconds (0 = the engine's own: MI355X_TIMEOUT_S, "
                  "else one day -- MPI's waits are unbounded; a rank whose process is gone is noticed without it)",
                  OPAL_INFO_LVL_9, &mca_coll_mi355x_timeout_s);

@@ -64,6 +64,13 @@
 
 using namespace mi355x;
 
+// MI355X_MOVE_ROW_LEVELS at creation: 1 or 2, anything else is the default
+static int env_row_levels()
+{
+    const double v = env_double("MI355X_MOVE_ROW_LEVELS", (double)kMoveRowLevelsDefault);
+    return v == 1.0 ? 1 : v == 2.0 ? 2 : kMoveRowLevelsDefault;
+}
+
 extern "C" {
 
 
@@ -186,6 +193,7 @@ int mi355x_comm_create(const char *key, int rank, int size, int device, mi355x_c
     c->nb_order = env_double("MI355X_NB_ORDER", 0.0) != 0.0 ? 1 : 0;
     c->scan_part_min = (size_t)std::max(0.0, env_double("MI355X_SCAN_PART_MIN_BYTES", (double)kScanPartMinDefault));
     c->move_send_min_run = (size_t)std::max(0.0, env_double("MI355X_MOVE_SEND_MIN_RUN", (double)kMoveSendMinRunDefault));
+    c->move_row_levels = env_row_levels();
     c->lat_on = env_double("MI355X_LAT_PROFILE", 0.0) != 0.0;
     c->rcache_max_maps = (size_t)std::max(0.0, env_double("MI355X_RCACHE_MAX_MAPS", 0.0));
     c->rcache_limit = (size_t)std::max(0.0, env_double("MI355X_RCACHE_SIZE_LIMIT", 0.0));
@@ -222,6 +230,7 @@ int mi355x_comm_create_loopback(int size, int device, mi355x_comm_t **comms)
         c->nb_order = env_double("MI355X_NB_ORDER", 0.0) != 0.0 ? 1 : 0;
         c->scan_part_min = (size_t)std::max(0.0, env_double("MI355X_SCAN_PART_MIN_BYTES", (double)kScanPartMinDefault));
         c->move_send_min_run = (size_t)std::max(0.0, env_double("MI355X_MOVE_SEND_MIN_RUN", (double)kMoveSendMinRunDefault));
+        c->move_row_levels = env_row_levels();
         shared->refs++;
         comms[r] = c;
     }
@@ -490,6 +499,8 @@ int mi355x_comm_get(const mi355x_comm_t *c, int knob, long *value)
     case MI355X_KNOB_MOVE_FUSED: *value = (long)c->move_fused; break;
     case MI355X_KNOB_MOVE_SEND_DIRECT: *value = (long)c->move_send_direct; break;
     case MI355X_KNOB_MOVE_SEND_MIN_RUN: *value = (long)c->move_send_min_run; break;
+    case MI355X_KNOB_MOVE_ROW_LEVELS: *value = c->move_row_levels; break;
+    case MI355X_KNOB_MOVE_PULL_LAUNCHES: *value = (long)c->move_pull_launches; break;
     default: return set_error(MI355X_ERR_ARG, "unknown knob %d", knob);
     }
     return MI355X_SUCCESS;
@@ -632,6 +643,11 @@ int mi355x_comm_set(mi355x_comm_t *c, int knob, long value)
         // (the sender's choice alone: receivers serve either record, so the ranks need not agree)
         if (value < 0) return set_error(MI355X_ERR_ARG, "move_send_min_run out of range");
         c->move_send_min_run = (size_t)value;
+        break;
+    case MI355X_KNOB_MOVE_ROW_LEVELS:
+        // (this rank's choice alone, as MOVE_SEND_MIN_RUN: a receiver serves whatever record it finds)
+        if (value != 1 && value != 2) return set_error(MI355X_ERR_ARG, "move_row_levels out of range");
+        c->move_row_levels = (int)value;
         break;
     case MI355X_KNOB_STAGE_BYTES:
         if (value < 4096 || value >= (1l << 31)) return set_error(MI355X_ERR_ARG, "stage_bytes out of range");

@@ -25,15 +25,35 @@
 
 namespace mi355x {
 
+static int rows2_table(mi355x_comm *c, Rows2Table *t);
+
+// ddt_unpack_segments for this communicator: its launch count and -- under MOVE_ROW_LEVELS = 2, and
+// only where the layout can use it (rows of the normal form that are not one run per block) -- its
+// piece table, which puts all pieces into one launch
+static int unpack_segments(mi355x_comm *c, const mi355x_ddt *rddt, const void *const *src, void *const *mem,
+                           const size_t *len, int nseg, hipStream_t s)
+{
+    Rows2Table tab{nullptr, nullptr};
+    const bool levels = c->move_row_levels >= 2 && mi355x_ddt_nruns(rddt) != 1 && mi355x_ddt_row_levels(rddt) != 0;
+    if (levels) {
+        const int rc = rows2_table(c, &tab);
+        if (rc) return rc;
+    }
+    return ddt_unpack_segments(rddt, src, mem, len, nseg, s, levels ? &tab : nullptr, &c->move_pull_launches);
+}
+
 // The pull.  Plain bytes: k_multicopy.  With a receive layout (the _ddt forms) the segments' bytes
 // are packed streams of `rddt`, each unpacked from where it lies -- the owner's memory -- into the
 // layout at its destination (ddt_unpack_segments): no dense receive view, no second pass.
 static int copy_segments(mi355x_comm *c, MultiCopyArgs &m, hipStream_t s, const mi355x_ddt *rddt = nullptr)
 {
     if (m.nseg == 0) return MI355X_SUCCESS;
-    if (!rddt) return launch_multicopy(m, s);
+    if (!rddt) {
+        c->move_pull_launches++;
+        return launch_multicopy(m, s);
+    }
     c->move_fused++;
-    return ddt_unpack_segments(rddt, m.src, m.dst, m.len, m.nseg, s);
+    return unpack_segments(c, rddt, m.src, m.dst, m.len, m.nseg, s);
 }
 
 // The receive side of a _ddt form as the impls take it.  A layout with gaps stays (d); a NULL one,
@@ -97,14 +117,14 @@ struct SendSide {
         : counts(cnt), displs(dsp)
     {
         if (!sddt || !cnt) return;
-        const SendShape sh = ddt_send_shape(sddt);
+        const SendShape sh = ddt_send_shape(sddt, c->move_row_levels);
         size_t most = 0;
         for (int q = 0; q < n; ++q) most = std::max(most, cnt[q]);
         const bool gap_free = send_gap_free(sh, most);
         if (!gap_free && !move_send_direct_ok(sh, cnt, nullptr, n, sbuf == nullptr, (int64_t)c->move_send_min_run)) {
             rc = set_error(MI355X_ERR_UNSUPPORTED, "%s: the send layout is not pulled from directly (%d runs per block, run %lld B, "
-                           "MOVE_SEND_MIN_RUN %zu%s): pack it", call, sh.nruns, (long long)sh.lay.run, c->move_send_min_run,
-                           sbuf ? "" : ", MPI_IN_PLACE");
+                           "MOVE_SEND_MIN_RUN %zu, MOVE_ROW_LEVELS %d%s): pack it", call, sh.nruns, (long long)sh.lay.run,
+                           c->move_send_min_run, c->move_row_levels, sbuf ? "" : ", MPI_IN_PLACE");
             return;
         }
         bytes.resize(2 * (size_t)n);
@@ -114,8 +134,8 @@ struct SendSide {
             bytes[(size_t)q] = cnt[q] * (size_t)sh.size;
             bytes[(size_t)(n + q)] = at + (gap_free ? (size_t)sh.lay.disp : 0);
             if (cnt[q])
-                reach = std::max(reach, at + (size_t)((int64_t)(cnt[q] - 1) * sh.lay.extent + (sh.lay.nblk - 1) * sh.lay.stride +
-                                                      sh.lay.disp + sh.lay.run));
+                reach = std::max(reach, at + (size_t)((int64_t)(cnt[q] - 1) * sh.lay.extent + (sh.lay.n1 - 1) * sh.lay.step1 +
+                                                      (sh.lay.nblk - 1) * sh.lay.stride + sh.lay.disp + sh.lay.run));
         }
         counts = bytes.data();
         if (dsp) displs = bytes.data() + n;
@@ -148,7 +168,8 @@ static int add_piece(Pull &p, const void *src, const RankSlot &owner, void *dst,
 {
     const RowLay &l = owner.slay;
     if (len == 0 || (l.nblk == 0 && src == dst)) return MI355X_SUCCESS;
-    if (l.nblk < 0 || (l.nblk && (l.run <= 0 || l.disp < 0 || l.nblk >= ((int64_t)1 << 32) || l.run >= ((int64_t)1 << 32))))
+    if (l.nblk < 0 || (l.nblk && (l.run <= 0 || l.disp < 0 || l.nblk >= ((int64_t)1 << 32) || l.run >= ((int64_t)1 << 32) ||
+                                  l.n1 < 1 || l.n1 >= ((int64_t)1 << 32))))
         return set_error(MI355X_ERR_PEER, "a peer published a send layout this rank cannot read");
     p.m.src[p.m.nseg] = src;
     p.m.dst[p.m.nseg] = dst;
@@ -159,6 +180,7 @@ static int add_piece(Pull &p, const void *src, const RankSlot &owner, void *dst,
     return MI355X_SUCCESS;
 }
 
+// the two-ended row gather's piece table, made at the first pull that needs one
 static int rows2_table(mi355x_comm *c, Rows2Table *t)
 {
     if (!c->rows2_dev) MI_HIP(hipMalloc(&c->rows2_dev, kRows2TableBytes));
@@ -171,7 +193,8 @@ static int rows2_table(mi355x_comm *c, Rows2Table *t)
 // The pull, whatever the owners published.  No send layout among the pieces: copy_segments, the
 // kernels of the plain and _ddt forms.  Otherwise one launch of the two-ended row gather
 // (ddt_gather_segments) for all pieces, dense ones included, into rddt or dense bytes.  When that
-// declines -- rddt has several runs per block, or an end is beyond the 32-bit slot arithmetic -- the
+// declines -- rddt is a run list (or rows that this rank's MOVE_ROW_LEVELS keeps off the launch), or
+// an end is beyond the 32-bit slot arithmetic -- the
 // dense pieces take copy_segments' kernels and the row pieces a launch of their own; and when rddt
 // is what it cannot take, the row pieces are gathered into the scratch as dense bytes (a dense
 // destination always applies to what move_send_direct_ok let a sender publish) and unpacked from
@@ -186,7 +209,7 @@ static int pull_segments(mi355x_comm *c, Pull &p, hipStream_t s, const mi355x_dd
     const int n = p.m.nseg;
     Row2Seg all[kMaxSegs];
     for (int i = 0; i < n; ++i) all[i] = Row2Seg{p.m.src[i], p.sl[i], p.m.dst[i], p.m.len[i]};
-    rc = ddt_gather_segments(rddt, all, n, tab, s);
+    rc = ddt_gather_segments(rddt, all, n, tab, s, c->move_row_levels, &c->move_pull_launches);
     if (rc != 1) return rc;
     MultiCopyArgs dn;
     std::memset(&dn, 0, sizeof(dn));
@@ -197,10 +220,11 @@ static int pull_segments(mi355x_comm *c, Pull &p, hipStream_t s, const mi355x_dd
         else add_seg(dn, p.m.src[i], p.m.dst[i], p.m.len[i]);
     }
     if (dn.nseg) {
-        rc = rddt ? ddt_unpack_segments(rddt, dn.src, dn.dst, dn.len, dn.nseg, s) : launch_multicopy(dn, s);
+        if (!rddt) c->move_pull_launches++;
+        rc = rddt ? unpack_segments(c, rddt, dn.src, dn.dst, dn.len, dn.nseg, s) : launch_multicopy(dn, s);
         if (rc) return rc;
     }
-    rc = ddt_gather_segments(rddt, rw, nr, tab, s);
+    rc = ddt_gather_segments(rddt, rw, nr, tab, s, c->move_row_levels, &c->move_pull_launches);
     if (rc != 1) return rc;
     if (!rddt) return set_error(MI355X_ERR_UNSUPPORTED, "a published send layout is beyond the row gather's limits");
     // two passes.  (The scratch is free: only alltoallv in place publishes it, and in place takes no rddt)
@@ -219,10 +243,10 @@ static int pull_segments(mi355x_comm *c, Pull &p, hipStream_t s, const mi355x_dd
         dsrc[i] = rw[i].mem;
         total += (rw[i].len + 15) & ~(size_t)15;
     }
-    rc = ddt_gather_segments(nullptr, rw, nr, tab, s);
+    rc = ddt_gather_segments(nullptr, rw, nr, tab, s, c->move_row_levels, &c->move_pull_launches);
     if (rc == 1) rc = set_error(MI355X_ERR_UNSUPPORTED, "a published send layout is beyond the row gather's limits");
     if (rc) return rc;
-    return ddt_unpack_segments(rddt, dsrc, dmem, dlen, nr, s);
+    return unpack_segments(c, rddt, dsrc, dmem, dlen, nr, s);
 }
 
 static int check_comm(mi355x_comm *c, int root)
@@ -730,7 +754,7 @@ int mi355x_alltoallv_ddt2(mi355x_comm_t *c, const void *sbuf, const mi355x_ddt_t
     DeviceGuard dg(c->device);
     if (sddt && sbuf && (!scounts || !sdispls)) return set_error(MI355X_ERR_ARG, "alltoallv: counts are NULL");
     // (in place the send arguments are not read: only a layout with gaps is refused, as rddt's is)
-    if (sddt && !sbuf && !send_gap_free(ddt_send_shape(sddt), 2))
+    if (sddt && !sbuf && !send_gap_free(ddt_send_shape(sddt, c->move_row_levels), 2))
         return set_error(MI355X_ERR_UNSUPPORTED, "alltoallv: MPI_IN_PLACE with a send layout");
     const SendSide sn(c, "alltoallv", sbuf, sbuf ? sddt : nullptr, c->size, scounts, sdispls);
     if (sn.rc) return sn.rc;
@@ -743,7 +767,8 @@ int mi355x_alltoallv_ddt2(mi355x_comm_t *c, const void *sbuf, const mi355x_ddt_t
 int mi355x_move_send_direct_ok(const mi355x_comm_t *c, const mi355x_ddt_t *sddt, const size_t *scounts, int n)
 {
     if (!c || !sddt || n < 0 || (n && !scounts)) return set_error(MI355X_ERR_ARG, "bad send layout arguments");
-    return move_send_direct_ok(ddt_send_shape(sddt), scounts, nullptr, n, false, (int64_t)c->move_send_min_run) ? 1 : 0;
+    return move_send_direct_ok(ddt_send_shape(sddt, c->move_row_levels), scounts, nullptr, n, false,
+                               (int64_t)c->move_send_min_run) ? 1 : 0;
 }
 
 int mi355x_alltoall(mi355x_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, void *stream)

@@ -52,6 +52,8 @@ constexpr double kDefaultTimeoutS = 86400.0;
 constexpr size_t kScanPartMinDefault = 0;
 // default of MI355X_KNOB_MOVE_SEND_MIN_RUN; measured, see BASELINE.md ("Pulling out of a send layout")
 constexpr size_t kMoveSendMinRunDefault = 16;
+// default of MI355X_KNOB_MOVE_ROW_LEVELS; measured, see BASELINE.md ("Pulling through 3-D subarray layouts")
+constexpr int kMoveRowLevelsDefault = 2;
 constexpr int kVoteRing = 64;   // buffer-kind votes a rank keeps (mi355x_comm_vote)
 constexpr int kVoteWindow = 32;  // calls per vote window: every rank waits at each window's last call
 
@@ -427,6 +429,10 @@ struct mi355x_comm {
     // MI355X_KNOB_MOVE_SEND_MIN_RUN (env MI355X_MOVE_SEND_MIN_RUN): the shortest run, in bytes, of a send
     // layout this rank publishes instead of packing; 0 = never.  The sender's choice alone
     size_t move_send_min_run = mi355x::kMoveSendMinRunDefault;
+    // MI355X_KNOB_MOVE_ROW_LEVELS (env MI355X_MOVE_ROW_LEVELS): 2 reads row layouts of up to two levels
+    // (row_levels_view) on both sides of the movement calls; 1 only what was rows before there were levels
+    int move_row_levels = mi355x::kMoveRowLevelsDefault;
+    uint64_t move_pull_launches = 0;              // kernels this communicator's movement pulls have launched
     void *rows2_dev = nullptr, *rows2_host = nullptr;  // the row gather's piece table (ddt_internal.hpp: Rows2Table)
     // finish() by device-written completion words (see RankSlot::done): the control segment
     // registered with HIP (hipHostRegister) and its device address; 0 = stream sync + barrier

@@ -279,69 +279,95 @@ bool ddt_contiguous(const mi355x_ddt *d, size_t count, int64_t *first)
     return count <= 1 || d->extent == d->nblk * len;
 }
 
+// The layout as rows, when it is rows (the levels; 0: a run list): the normal form of its tables
+// (row_levels_view, ddt_rows_plan.hpp) -- one run per block; one block whose runs all have one
+// length and one spacing, what a column is compiled to from opal's optimized description (one ELEM
+// record of strided elements, unrolled into runs); or, with a second level, the pencil of a 3-D
+// array: several equal runs per block at one spacing, or one block whose runs are a two-level
+// progression.  Only the movement collectives read a layout this way: pack and unpack keep the
+// kernels their run tables select.
+static int row_view(const mi355x_ddt *d, RowLay *l, int max_levels = 2)
+{
+    return row_levels_view(d->disp.data(), d->len.data(), d->disp.size(), d->nblk, d->stride, d->extent, l, max_levels);
+}
+
 int ddt_unpack_segments(const mi355x_ddt *d, const void *const *src, void *const *mem, const size_t *len, int nseg,
-                        hipStream_t s)
+                        hipStream_t s, const Rows2Table *tab, uint64_t *launches)
 {
     if (!d || nseg < 0 || nseg > kRowsMaxSegs) return set_error(MI355X_ERR_ARG, "bad unpack segments");
     if (nseg == 0 || d->nblk * blk_bytes(d) == 0) return MI355X_SUCCESS;
     int rc = upload(const_cast<mi355x_ddt *>(d));
     if (rc) return rc;
     const DdtDev dv = dev_view(d);
-    RowSeg segs[kRowsMaxSegs];
-    for (int i = 0; i < nseg; ++i) segs[i] = RowSeg{src[i], mem[i], len[i]};
+    int live = 0;  // pieces that move bytes
+    for (int i = 0; i < nseg; ++i) live += len[i] != 0 && src[i] != mem[i];
+    uint64_t none = 0;
+    uint64_t &nl = launches ? *launches : none;
     const bool row = d->disp.size() == 1;
-    rc = row ? launch_ddt_rows_multi(dv, d->disp[0], d->len[0], segs, nseg, s) : 1;
+    rc = 1;
+    if (row) {
+        RowSeg segs[kRowsMaxSegs];
+        for (int i = 0; i < nseg; ++i) segs[i] = RowSeg{src[i], mem[i], len[i]};
+        rc = launch_ddt_rows_multi(dv, d->disp[0], d->len[0], segs, nseg, s);
+    } else if (tab) {
+        // rows only the normal form reads as rows: the two-ended gather, every source dense
+        RowLay dst;
+        if (row_view(d, &dst)) {
+            Row2Seg segs[kRowsMaxSegs];
+            int n = 0;
+            for (int i = 0; i < nseg; ++i)
+                if (len[i] != 0 && src[i] != mem[i]) segs[n++] = Row2Seg{src[i], row_dense(), mem[i], len[i]};
+            rc = n ? launch_ddt_rows2_multi(dst, segs, n, *tab, s) : MI355X_SUCCESS;
+        }
+    }
+    if (rc == MI355X_SUCCESS && live) nl++;
     if (rc != 1) return rc;
-    // several runs per block (the unit / runs / general kernels), or a row layout the one launch
-    // does not take: piece by piece, as mi355x_unpack would, still straight from the source
+    // a run list (the unit / runs / general kernels), or a row layout the one launch does not take:
+    // piece by piece, as mi355x_unpack would, still straight from the source
     for (int i = 0; i < nseg; ++i) {
         if (len[i] == 0 || src[i] == mem[i]) continue;
         void *pk = const_cast<void *>(src[i]);
         rc = row ? launch_ddt_rows(dv, 1, d->disp[0], d->len[0], false, mem[i], pk, 0, (int64_t)len[i], nullptr, s) : 1;
         if (rc == 1) rc = launch_ddt(dv, false, mem[i], pk, 0, (int64_t)len[i], nullptr, s);
         if (rc) return rc;
+        nl++;
     }
     return MI355X_SUCCESS;
 }
 
-// The layout as rows, when it is rows: one run per block; or one block whose runs all have one
-// length and one spacing -- what a column is compiled to from opal's optimized description (one
-// ELEM record of strided elements, unrolled into runs), the same bytes in the same packed order as
-// nruns blocks of one run.  Only the two-ended gather reads a layout this way: pack, unpack and the
-// _ddt forms keep the kernels their run tables select.
-static bool row_view(const mi355x_ddt *d, RowLay *l)
-{
-    const size_t n = d->disp.size();
-    *l = RowLay{d->nblk, d->disp[0], d->len[0], d->stride, d->extent};
-    if (n == 1) return d->len[0] > 0;
-    if (d->nblk != 1 || d->len[0] <= 0) return false;
-    const int64_t step = d->disp[1] - d->disp[0];
-    for (size_t r = 1; r < n; ++r)
-        if (d->len[r] != d->len[0] || d->disp[r] - d->disp[r - 1] != step) return false;
-    *l = RowLay{(int64_t)n, d->disp[0], d->len[0], step, d->extent};
-    return true;
-}
-
-SendShape ddt_send_shape(const mi355x_ddt *d)
+SendShape ddt_send_shape(const mi355x_ddt *d, int max_levels)
 {
     SendShape sh;
-    sh.nruns = row_view(d, &sh.lay) ? 1 : (int)d->disp.size();
+    sh.nruns = row_view(d, &sh.lay, max_levels) ? 1 : (int)d->disp.size();
     sh.size = d->nblk * blk_bytes(d);
     return sh;
 }
 
-int ddt_gather_segments(const mi355x_ddt *d, const Row2Seg *segs, int nseg, const Rows2Table &tab, hipStream_t s)
+int ddt_gather_segments(const mi355x_ddt *d, const Row2Seg *segs, int nseg, const Rows2Table &tab, hipStream_t s,
+                        int max_levels, uint64_t *launches)
 {
     if (nseg < 0 || nseg > kRowsMaxSegs) return set_error(MI355X_ERR_ARG, "bad gather segments");
     if (nseg == 0) return MI355X_SUCCESS;
-    if (!d) return launch_ddt_rows2_multi(row_dense(), segs, nseg, tab, s);
-    RowLay dst;
-    if (!row_view(d, &dst)) return 1;
-    return launch_ddt_rows2_multi(dst, segs, nseg, tab, s);
+    RowLay dst = row_dense();
+    if (d && !row_view(d, &dst, max_levels)) return 1;
+    const int rc = launch_ddt_rows2_multi(dst, segs, nseg, tab, s);
+    if (rc == MI355X_SUCCESS && launches)
+        for (int i = 0; i < nseg; ++i)
+            if (segs[i].len) {
+                ++*launches;
+                break;
+            }
+    return rc;
 }
 } // namespace mi355x
 
 extern "C" {
+
+int mi355x_ddt_row_levels(const mi355x_ddt_t *d)
+{
+    RowLay l;
+    return d && !d->disp.empty() ? row_view(d, &l) : 0;
+}
 
 int mi355x_ddt_tune(int unroll_pack, int unroll_unpack, int threads, int nontemporal)
 {

@@ -56,16 +56,21 @@ int launch_ddt_rows_multi(const DdtDev &d, int64_t run_disp, int64_t run_len, co
                           hipStream_t s);
 // the pull of a movement collective into a receive layout (coll_move.cpp): piece i = len[i] packed
 // bytes at src[i], which may be a peer's mapped memory, unpacked into d laid at mem[i].  A row
-// layout takes one launch; any other goes piece by piece through launch_ddt (not yet one launch).
-// Nothing is waited for.
+// layout takes one launch: k_ddt_rows_multi when its tables hold one run per block, else -- rows of
+// up to two levels in the normal form (row_levels_view), and a piece table given (the caller gives
+// none under MI355X_KNOB_MOVE_ROW_LEVELS = 1) -- the two-ended row gather with dense sources.  Any
+// other goes piece by piece through launch_ddt.  *launches (may be NULL) grows by the kernels
+// launched.  Nothing is waited for.
+struct Rows2Table;
 int ddt_unpack_segments(const mi355x_ddt *d, const void *const *src, void *const *mem, const size_t *len, int nseg,
-                        hipStream_t s);
+                        hipStream_t s, const Rows2Table *tab = nullptr, uint64_t *launches = nullptr);
 
-// the eligibility rule's view of a layout (ddt_rows_plan.hpp: move_send_direct_ok)
-SendShape ddt_send_shape(const mi355x_ddt *d);
+// the eligibility rule's view of a layout (ddt_rows_plan.hpp: move_send_direct_ok); max_levels 1
+// reads as rows only what was rows before there were levels (row_levels_view)
+SendShape ddt_send_shape(const mi355x_ddt *d, int max_levels = 2);
 // the two-ended row gather's per-piece table: device memory the kernel reads, and the pinned host
 // copy it is filled in (both kRows2TableBytes; the communicator owns them, coll_move.cpp)
-constexpr size_t kRows2TableBytes = 64 * (size_t)kRowsMaxSegs;
+constexpr size_t kRows2TableBytes = 96 * (size_t)kRowsMaxSegs;
 struct Rows2Table {
     void *dev, *host;
 };
@@ -74,9 +79,11 @@ struct Rows2Table {
 int launch_ddt_rows2_multi(const RowLay &dst, const Row2Seg *segs, int nseg, const Rows2Table &tab, hipStream_t s);
 // the pull of a movement collective out of published send layouts: piece i = segs[i].len bytes read
 // through segs[i].s at segs[i].src, written through d laid at segs[i].mem (d NULL: dense bytes).  One
-// launch; returns 1 when it does not apply -- d has several runs per block, or the plan declines --
-// and the caller gathers into dense scratch first.  mi355x_ddt_tune_rows is not consulted: a receiver
-// serves whatever a sender was allowed to publish.  Nothing is waited for.
-int ddt_gather_segments(const mi355x_ddt *d, const Row2Seg *segs, int nseg, const Rows2Table &tab, hipStream_t s);
+// launch; returns 1 when it does not apply -- d is a run list (or rows that max_levels keeps off the
+// launch), or the plan declines -- and the caller gathers into dense scratch first.
+// mi355x_ddt_tune_rows is not consulted: a receiver serves whatever a sender was allowed to publish.
+// *launches as above.  Nothing is waited for.
+int ddt_gather_segments(const mi355x_ddt *d, const Row2Seg *segs, int nseg, const Rows2Table &tab, hipStream_t s,
+                        int max_levels = 2, uint64_t *launches = nullptr);
 
 } // namespace mi355x

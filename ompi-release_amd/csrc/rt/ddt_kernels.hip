@@ -524,12 +524,13 @@ int launch_ddt_rows_multi(const DdtDev &d, int64_t run_disp, int64_t run_len, co
 // owner's record) and written at the address the receiver's one DESTINATION layout gives it (the
 // same two divisions) -- read once where the sender's application left it, written once where the
 // receiver's wants it.  Only the source may be remote, and it is only read; stores are local
-// (k_ddt_rows_multi's rule).  A dense end is the degenerate layout, one row: the destination's
-// divisions are templated away (DROWS), a dense piece among row pieces takes the pass without the
-// source divisions by a branch that is uniform per block.
+// (k_ddt_rows_multi's rule).  Either end may have a second level (rows in groups: the pencil of a
+// 3-D array), which costs that end one more division.  A dense end is the degenerate layout, one
+// row: the destination's levels are a template parameter (DLEV: 0 dense, 1 rows, 2 rows in groups),
+// the source's a word of the piece's entry, taken by a branch that is uniform per block.
 // The slot mapping (row_slot_off) lives in ddt_rows_plan.hpp, where the host check runs it against
 // a byte-by-byte enumeration of both layouts.
-// The per-piece table (two pointers, the source's strides and magic numbers: 64 B a piece, 4 KiB
+// The per-piece table (two pointers, the source's steps and magic numbers: 96 B a piece, 6 KiB
 // for 64 pieces) does not fit HIP's kernel arguments beside first_block[]; it lies in device memory
 // (copied on the call's stream from the communicator's pinned staging copy) and a block reads the
 // ONE entry of its piece, with wave-uniform loads, after finding the piece in first_block[] (by
@@ -539,8 +540,9 @@ struct alignas(16) Rows2Piece {
     char *dst;        // ... the destination's
     RowEnd s;
     uint32_t nslots;
-    uint32_t s_rows;  // 0: the source is dense
+    uint32_t s_lev;   // the source's levels (row_levels: 0 dense)
 };
+static_assert(sizeof(Rows2Piece) % 16 == 0, "entries keep their 16-byte alignment");
 static_assert(sizeof(Rows2Piece) * kRowsMaxSegs == kRows2TableBytes, "the communicator's table holds one launch");
 struct Rows2Args {
     const Rows2Piece *tab;
@@ -549,7 +551,7 @@ struct Rows2Args {
     unsigned first_block[kRowsMaxSegs + 1];
 };
 
-template <int NTM, int U, int W, bool SROWS, bool DROWS>
+template <int NTM, int U, int W, int SLEV, int DLEV>
 __device__ __forceinline__ void rows2_pass(const Rows2Piece &p, const RowEnd &d, uint32_t base, uint32_t tpb)
 {
     typedef typename SlotT<W>::type S;
@@ -560,8 +562,8 @@ __device__ __forceinline__ void rows2_pass(const Rows2Piece &p, const RowEnd &d,
         const uint32_t i = base + (uint32_t)u * tpb;
         dp[u] = nullptr;
         if (i < p.nslots) {
-            const S *src = reinterpret_cast<const S *>(p.src + row_slot_off<W, SROWS>(p.s, i));
-            dp[u] = p.dst + row_slot_off<W, DROWS>(d, i);
+            const S *src = reinterpret_cast<const S *>(p.src + row_slot_off<W, SLEV>(p.s, i));
+            dp[u] = p.dst + row_slot_off<W, DLEV>(d, i);
             if constexpr ((NTM & 1) != 0) v[u] = __builtin_nontemporal_load(src);
             else v[u] = *src;
         }
@@ -576,7 +578,7 @@ __device__ __forceinline__ void rows2_pass(const Rows2Piece &p, const RowEnd &d,
     }
 }
 
-template <int NTM, int U, int W, bool DROWS>
+template <int NTM, int U, int W, int DLEV>
 __global__ __launch_bounds__(256) void k_ddt_rows2_multi(Rows2Args m)
 {
     int sgi = 0;
@@ -586,28 +588,31 @@ __global__ __launch_bounds__(256) void k_ddt_rows2_multi(Rows2Args m)
     const Rows2Piece p = m.tab[sgi];  // (uniform per block)
     const uint32_t tpb = blockDim.x;
     const uint64_t per = (uint64_t)tpb * U;
-    if (p.s_rows) {
+    if (p.s_lev == 2) {
         for (uint64_t base = (uint64_t)b * per + threadIdx.x; base < p.nslots; base += (uint64_t)nb * per)
-            rows2_pass<NTM, U, W, true, DROWS>(p, m.d, (uint32_t)base, tpb);
+            rows2_pass<NTM, U, W, 2, DLEV>(p, m.d, (uint32_t)base, tpb);
+    } else if (p.s_lev) {
+        for (uint64_t base = (uint64_t)b * per + threadIdx.x; base < p.nslots; base += (uint64_t)nb * per)
+            rows2_pass<NTM, U, W, 1, DLEV>(p, m.d, (uint32_t)base, tpb);
     } else {
         for (uint64_t base = (uint64_t)b * per + threadIdx.x; base < p.nslots; base += (uint64_t)nb * per)
-            rows2_pass<NTM, U, W, false, DROWS>(p, m.d, (uint32_t)base, tpb);
+            rows2_pass<NTM, U, W, 0, DLEV>(p, m.d, (uint32_t)base, tpb);
     }
 }
 
 constexpr unsigned kRows2Threads = 256;
 constexpr int kRows2Unroll16 = 4;  // slots per lane at W = 16 (kNarrowUnroll below it)
 
-template <int NTM, bool DROWS>
+template <int NTM, int DLEV>
 static void launch_rows2_w(int w, const Rows2Args &m, unsigned blocks, hipStream_t s)
 {
     const dim3 g(blocks), t(kRows2Threads);
     switch (w) {
-    case 16: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kRows2Unroll16, 16, DROWS>), g, t, 0, s, m); break;
-    case 8: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kNarrowUnroll, 8, DROWS>), g, t, 0, s, m); break;
-    case 4: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kNarrowUnroll, 4, DROWS>), g, t, 0, s, m); break;
-    case 2: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kNarrowUnroll, 2, DROWS>), g, t, 0, s, m); break;
-    default: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kNarrowUnroll, 1, DROWS>), g, t, 0, s, m); break;
+    case 16: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kRows2Unroll16, 16, DLEV>), g, t, 0, s, m); break;
+    case 8: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kNarrowUnroll, 8, DLEV>), g, t, 0, s, m); break;
+    case 4: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kNarrowUnroll, 4, DLEV>), g, t, 0, s, m); break;
+    case 2: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kNarrowUnroll, 2, DLEV>), g, t, 0, s, m); break;
+    default: hipLaunchKernelGGL((k_ddt_rows2_multi<NTM, kNarrowUnroll, 1, DLEV>), g, t, 0, s, m); break;
     }
 }
 
@@ -627,7 +632,7 @@ int launch_ddt_rows2_multi(const RowLay &dst, const Row2Seg *segs, int nseg, con
         e.dst = static_cast<char *>(g.mem) + (dst.nblk ? dst.disp : 0);
         e.s = row_end(g.s, p.w);
         e.nslots = (uint32_t)(g.len / (size_t)p.w);
-        e.s_rows = g.s.nblk ? 1u : 0u;
+        e.s_lev = (uint32_t)row_levels(g.s);
     }
     // the pinned copy is free again when the call that filled it returns (every movement call ends
     // at finish(): its stream has passed this copy and the kernel behind it)
@@ -640,12 +645,20 @@ int launch_ddt_rows2_multi(const RowLay &dst, const Row2Seg *segs, int nseg, con
     for (int i = 0; i <= p.nseg; ++i) m.first_block[i] = p.first_block[i];
     const unsigned blocks = p.first_block[p.nseg];
     // the load flavour and the non-temporal rule of launch_ddt_rows_multi
-    if (dst.nblk) {
-        if (beyond_mall(2 * p.total)) launch_rows2_w<3, true>(p.w, m, blocks, s);
-        else launch_rows2_w<0, true>(p.w, m, blocks, s);
-    } else {
-        if (beyond_mall(2 * p.total)) launch_rows2_w<3, false>(p.w, m, blocks, s);
-        else launch_rows2_w<0, false>(p.w, m, blocks, s);
+    const bool nt = beyond_mall(2 * p.total);
+    switch (row_levels(dst)) {
+    case 2:
+        if (nt) launch_rows2_w<3, 2>(p.w, m, blocks, s);
+        else launch_rows2_w<0, 2>(p.w, m, blocks, s);
+        break;
+    case 1:
+        if (nt) launch_rows2_w<3, 1>(p.w, m, blocks, s);
+        else launch_rows2_w<0, 1>(p.w, m, blocks, s);
+        break;
+    default:
+        if (nt) launch_rows2_w<3, 0>(p.w, m, blocks, s);
+        else launch_rows2_w<0, 0>(p.w, m, blocks, s);
+        break;
     }
     MI_HIP(hipGetLastError());
     return MI355X_SUCCESS;
